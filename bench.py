@@ -10,10 +10,12 @@ classifier + softmax-CE, full backward, dSGD all-reduce (RCCL over xGMI for N>1)
 Synthetic data (the ICA dataset is not shipped, ``.gitignore:123``) and random-init weights.
 
 The timed steps run through ``runtime.feed.DeviceFeed`` -- the object the production site loop
-(``runtime.site.FederatedSite``) trains its epochs with, per-step train records included.  At one
-site the run then trains a synthetic hard cohort through ``FederatedSite`` itself and adds the
-second half of the BASELINE metric, wall-clock to the target validation AUC
-(``time_to_auc_s``), and the site loop's own logged throughput (``site_loop_samples_per_sec``).
+(``runtime.site.FederatedSite``) trains its epochs with, per-step train records included.  A
+plain run does only that: set up, warm up, time ``--steps`` steps, write the last step's outputs
+when ``--dump-outputs DIR`` is given, print the result line.  With ``--full`` a one-site run then
+trains a synthetic hard cohort through ``FederatedSite`` itself and adds the second half of the
+BASELINE metric, wall-clock to the target validation AUC (``time_to_auc_s``), and the site
+loop's own logged throughput (``site_loop_samples_per_sec``).
 
 Launch: ``python bench.py`` (1 GPU) or ``python -m torch.distributed.run --nproc-per-node N
 --master-addr 127.0.0.1 bench.py --gpus N``.  Rank 0 prints ONE JSON line; ``value`` is the
@@ -56,11 +58,20 @@ def parse():
     ap.add_argument("--graph-steps", type=int, default=0,
                     help="steps per HIP graph in device-feed mode (0: the largest divisor of "
                          "--steps up to 10)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every further measurement of the "
+                         "benchmark (today: the site-loop study, see --site-loop); a plain run "
+                         "sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last "
+                         "step (loss, logits, predictions, per-step train records, updated "
+                         "parameters) as DIR/<name>.npy (rank 0; float32, at most 64 MB in all)")
     ap.add_argument("--site-loop", default="auto", choices=["auto", "0", "1"],
                     help="after the timed steps, train a synthetic hard ICA cohort through the "
                          "production site loop (runtime.site.FederatedSite: device-fed epochs, "
                          "validation, early stopping, checkpoints) and report its wall-clock to "
-                         "the target validation AUC and its logged samples/s (auto: N == 1)")
+                         "the target validation AUC and its logged samples/s (auto: with --full "
+                         "at N == 1; 1: always)")
     ap.add_argument("--target-auc", type=float, default=0.75)
     ap.add_argument("--tta-subjects", type=int, default=2560,
                     help="site-loop cohort size (split 0.8/0.1/0.1)")
@@ -142,6 +153,36 @@ def site_loop(grp, args):
     }
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(path, step, flat, feed=None):
+    """``--dump-outputs``: what the timed path handed its caller in the last timed step, one
+    float32 ``.npy`` per array: the step's loss, its logits / class probabilities (``out``) and
+    predictions, the updated flat parameter vector, and (device feed) the per-step loss and score
+    rings the site loop reads its train metrics from.  The inputs are seeded, so two builds run
+    with the same arguments can be compared array for array.  An array that would take the dump
+    past 64 MB is cut to a fixed seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": step.last_loss, "out": step.last_out, "pred": step.last_pred,
+              "params": flat.data}
+    if feed is not None:
+        arrays["step_losses"] = feed.rec.losses
+        arrays["step_scores"] = feed.rec.scores
+    left = DUMP_LIMIT_BYTES
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if a.nbytes > left // 2:
+            # a fixed sample: the same element indices for every build and run
+            idx = np.random.default_rng(0).choice(a.size, size=max(1, left // 8), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     from dinunet_implementations_amd.parallel import init_sites, make_engine
@@ -170,6 +211,7 @@ def main():
     ys = torch.randint(0, 2, (args.pool, args.batch), device=dev, generator=g)
 
     pi, it0 = getattr(engine, "power_iterations", None), None
+    feed = None
     if args.feed == "device":
         # the site's (synthetic) dataset resident in HBM as bf16, batches gathered on the device
         # by the step's first launch, per-step train records kept on the device: the same
@@ -215,15 +257,19 @@ def main():
     n = grp.world
     total = n * args.batch * args.steps / dt
     peak = torch.cuda.max_memory_allocated(dev)
+    if args.dump_outputs and grp.is_master:
+        dump_outputs(args.dump_outputs, step, flat, feed)
     tta = None
-    if args.site_loop == "1" or (args.site_loop == "auto" and n == 1 and not grp.loopback):
+    if args.site_loop == "1" or (args.site_loop == "auto" and args.full and n == 1
+                                 and not grp.loopback):
         try:
             tta = site_loop(grp, args)
         except Exception as e:  # never lose the throughput line to the study
             tta = {"time_to_auc_s": None, "site_loop_error": f"{type(e).__name__}: {e}"}
     else:
         tta = {"time_to_auc_s": None,
-               "site_loop": "not run (default at N > 1; --site-loop 1 runs it on every site)"}
+               "site_loop": "not run (--full runs it at N == 1; --site-loop 1 runs it on every "
+                            "site)"}
     if grp.is_master:
         rec = {
             # the headline metric names dSGD; other engines report the same quantity under

@@ -25,15 +25,21 @@ def pytest_collection_modifyitems(config, items):
             it.add_marker(skip)
 
 
-REF_DATA = "/root/reference/datasets/test_fsl"
+REF_DATA = os.path.join(ROOT, "tests", "golden", "test_fsl.tar.gz")
+
+
+@pytest.fixture(scope="session")
+def _fs_golden(tmp_path_factory):
+    """``tests/golden/test_fsl.tar.gz`` (the reference's ``datasets/test_fsl``: inputspec.json and
+    per site a covariate CSV plus one aseg-stats text file per subject) unpacked once per run."""
+    import tarfile
+    d = tmp_path_factory.mktemp("golden")
+    with tarfile.open(REF_DATA) as t:
+        t.extractall(d)
+    return str(d / "test_fsl")
 
 
 @pytest.fixture
-def fs_data_root():
-    """The reference's shipped 5-site FreeSurfer simulator data (read-only), or a synthetic copy."""
-    if os.path.isdir(REF_DATA):
-        return REF_DATA
-    from dinunet_implementations_amd.data.synthetic import make_fs_sites
-    import tempfile
-    d = tempfile.mkdtemp()
-    return make_fs_sites(d, sites=5, subjects=(40, 30, 50, 40, 60))
+def fs_data_root(_fs_golden):
+    """The reference's shipped 5-site FreeSurfer simulator data (read-only)."""
+    return _fs_golden

@@ -9,11 +9,26 @@ import torch.multiprocessing as mp
 
 
 def free_port() -> int:
+    # bound on every address, as the rendezvous server listens: a port that is free on
+    # 127.0.0.1 alone may be taken on another address of the host
     s = socket.socket()
-    s.bind(("127.0.0.1", 0))
+    s.bind(("", 0))
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def init_one_rank_rccl():
+    """The default process group as ONE RCCL rank on cuda:0.  Its store listens on a port the
+    server socket picks itself (port 0), so there is no window between finding a free port and
+    binding it in which another process of the host can take it."""
+    import torch
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    store = dist.TCPStore("127.0.0.1", 0, 1, is_master=True)
+    os.environ["MASTER_PORT"] = str(store.port)
+    dist.init_process_group("nccl", store=store, rank=0, world_size=1,
+                            device_id=torch.device("cuda", 0))
 
 
 def _entry(rank, world, port, fn, args, outdir, replicas=1):

@@ -81,11 +81,9 @@ def test_waiting_kernels_beside_busy_cus(engine, cfg, use_graph, monkeypatch):
     in-kernel wait may time out and training must match the undisturbed run."""
     import torch.distributed as dist
     from dinunet_implementations_amd.runtime import health
-    from test_step_gpu import _OneRankGroup, _batches, _free_port, _trainer
-    import os
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    from mp_util import init_one_rank_rccl
+    from test_step_gpu import _OneRankGroup, _batches, _trainer
+    init_one_rank_rccl()
     try:
         grp = _OneRankGroup(dist.group.WORLD)
         xs, ys = _batches()

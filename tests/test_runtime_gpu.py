@@ -4,11 +4,12 @@ once more with a 1-rank RCCL group that takes every collective code path (broadc
 all-reduce between split graphs, variable-length metric gathers, barriers)."""
 import json
 import os
-import socket
 
 import pytest
 import torch
 import torch.distributed as dist
+
+from mp_util import free_port, init_one_rank_rccl
 
 pytestmark = pytest.mark.gpu
 
@@ -52,19 +53,9 @@ def test_fs_site_on_gpu(fs_data_root, tmp_path):
     assert len(logs[0]["train_log"]) == 3 and logs[0]["test_metrics"]
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def test_ica_site_collective_paths_over_rccl(tmp_path):
     from test_step_gpu import _OneRankGroup
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    init_one_rank_rccl()
     try:
         root = _ica_root(tmp_path)
         out = str(tmp_path / "out")
@@ -124,7 +115,7 @@ def test_ica_two_sites_two_gpus_each_on_one_gpu(tmp_path, engine):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DINUNET_BACKEND="gloo", PYTHONPATH=repo, OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node",
-           "4", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "-m",
+           "4", "--master-addr", "127.0.0.1", "--master-port", str(free_port()), "-m",
            "dinunet_implementations_amd.run", "--data-path", root, "--out", out,
            "--site-gpus", "2", "--set", "epochs=2", "--set", "batch_size=8", "--set",
            f"agg_engine={engine}", "--set", "dad_reduction_rank=4", "--set",

@@ -1,12 +1,11 @@
 """TrainStep on the GPU: HIP-graph replay vs eager, split (two-graph) capture with the dSGD
 all-reduce launched between the replays over a real RCCL communicator, and the rank-dAD
 activation/delta capture of the fused kernels (``dW == Delta^T A`` for every Linear)."""
-import os
-import socket
-
 import pytest
 import torch
 import torch.distributed as dist
+
+from mp_util import init_one_rank_rccl
 
 pytestmark = pytest.mark.gpu
 
@@ -96,18 +95,8 @@ class _OneRankGroup:
         return G(rank=0, world=1, local_rank=0, device=torch.device("cuda", 0), backend="nccl", pg=pg)
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def test_split_capture_overlapped_allreduce_over_rccl():
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    init_one_rank_rccl()
     try:
         grp = _OneRankGroup(dist.group.WORLD)
         xs, ys = _batches()
@@ -126,9 +115,7 @@ def test_split_capture_overlapped_allreduce_over_rccl():
 @pytest.fixture
 def rccl1():
     """A one-rank RCCL process group the multi-site code paths run on (``_OneRankGroup``)."""
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(_free_port())
-    dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
+    init_one_rank_rccl()
     try:
         yield _OneRankGroup(dist.group.WORLD)
     finally:

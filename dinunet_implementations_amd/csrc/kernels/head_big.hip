@@ -27,6 +27,11 @@
 //         bias gradient.
 //       bn(l) (row blocks): merges the column sums (= d beta, d gamma) and writes
 //         dZ_l = gamma rstd (dy - mean(dy) - xhat mean(dy xhat)).
+// A LayerNorm layer (norm mode 3) reduces along a row, which the row block x column block grid
+// splits over workgroups: fwd(l) is followed by ln(l) (a wave per row: xhat over Z_l, rstd per row)
+// and the consumer applies gamma / beta where it applies a BatchNorm's scale / shift; in the
+// backward ln_bwd(l) stands where bn(l) does (same per-row-block partials for d gamma / d beta, and
+// the bias gradient partials are sums of the real dZ_l).
 // The last layer must be a plain Linear (no BatchNorm / ReLU after the logits), as in both heads.
 #include "head_common.h"
 
@@ -59,7 +64,8 @@ struct BLayer {
   float* ggamma;
   float* gbeta;
   int in, out;
-  int bn;      // 0 none, 1 batch statistics always, 2 batch statistics + running update / running
+  int bn;      // 0 none, 1 batch statistics always, 2 batch statistics + running update / running,
+               // 3 LayerNorm over the out features (Z_l holds xhat after headb_ln_fwd_kernel)
   int relu;
   float drop;  // dropout on this layer's INPUT (training only)
   float eps, momentum;
@@ -67,7 +73,7 @@ struct BLayer {
   long a_off;    // bf16 [B][S_a] input activations (post dropout)
   long z_off;    // fp32 [B][out] pre-BatchNorm outputs (bias included)
   long part_off; // F2 [nrb][out] per-row-block (mean, M2)
-  long stat_off; // F2 [out] (mean, rstd) of the forward
+  long stat_off; // F2 [out] (mean, rstd) of the forward; LayerNorm: fp32 [B] per-row rstd
   long dy_off;   // fp32 [B][out] d loss / d BN output (post ReLU mask)
   long part2_off;  // F2 [nrb][out] per-row-block (sum dy, sum dy xhat)
   long dz_off;   // bf16 [B][S_z] d loss / d Z
@@ -153,6 +159,11 @@ __device__ __forceinline__ void bn_affine(const BArgs& a, const BLayer& P, const
   s = 1.f;
   t = 0.f;
   if (!P.bn) return;
+  if (P.bn == 3) {  // LayerNorm: headb_ln_fwd_kernel left xhat in Z, the affine is gamma / beta
+    s = P.gamma[k];
+    t = P.beta[k];
+    return;
+  }
   const bool train = a.train != 0;
   // the affine parameters and running statistics are loaded with the partials, not after the
   // merge (each was one more dependent round trip before the first chunk)
@@ -334,6 +345,101 @@ headb_fwd_kernel(BArgs a, int l, const float* __restrict__ x, long ldx,
       }
     m2 = colsum4(m2);
     if (lane < 16 && cv) reinterpret_cast<F2*>(ws + L.part_off)[(long)rb * N + n] = F2{mean, m2};
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// LayerNorm of layer l (norm mode 3), the launch after fwd(l): one wave per row takes the row's
+// (mean, biased var) over the N columns of the fp32 Z_l (two passes, lane-strided partials +
+// butterfly: a fixed order), writes xhat back over Z_l and the row's rstd for the backward.  The
+// consumer's staging then applies gamma / beta per column exactly as it applies a BatchNorm's
+// scale / shift (bn_affine).
+__global__ void __launch_bounds__(BNT)
+headb_ln_fwd_kernel(BArgs a, int l, char* __restrict__ ws) {
+  const BLayer& L = a.L[l];
+  const int N = L.out, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (BNT / 64) + (threadIdx.x >> 6);
+  if (row >= a.B) return;
+  float* zr = reinterpret_cast<float*>(ws + L.z_off) + (long)row * N;
+  float s = 0.f;
+  for (int c = lane; c < N; c += 64) s += zr[c];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+  const float mean = s / (float)N;
+  float v = 0.f;
+  for (int c = lane; c < N; c += 64) {
+    const float d = zr[c] - mean;
+    v += d * d;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  const float rstd = rsqrtf(v / (float)N + L.eps);
+  for (int c = lane; c < N; c += 64) zr[c] = (zr[c] - mean) * rstd;
+  if (lane == 0) reinterpret_cast<float*>(ws + L.stat_off)[row] = rstd;
+}
+
+// LayerNorm backward of layer l, one workgroup per 64-row block (in place of headb_bn_bwd_kernel):
+// block 0 first merges the per-row-block column sums of the dA epilogue (sum dy = d beta,
+// sum dy xhat = d gamma) in row-block order; every block then runs its rows, a wave per row:
+// g = dy gamma, dz = rstd (g - mean(g) - xhat mean(g xhat)) into the bf16 image and, in fp32, back
+// over dy; after a barrier a thread per column adds the block's rows of dz in order into the
+// bias-gradient partials.
+__global__ void __launch_bounds__(BNT)
+headb_ln_bwd_kernel(BArgs a, int l, char* __restrict__ ws, RedJob rj) {
+  if (rj.rl >= 0 && (int)blockIdx.x >= rj.r0) {
+    dw_reduce_body(a, rj.rl, ws, rj.rs, blockIdx.x - rj.r0, gridDim.x - rj.r0);
+    return;
+  }
+  const BLayer& L = a.L[l];
+  const int N = L.out, B = a.B, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  if (blockIdx.x == 0) {
+    const F2* part2 = reinterpret_cast<const F2*>(ws + L.part2_off);
+    for (int c = tid; c < N; c += BNT) {
+      float s1 = 0.f, s2 = 0.f;
+      for (int rb = 0; rb < a.nrb; ++rb) {
+        const F2 q = part2[(long)rb * N + c];
+        s1 += q.x;
+        s2 += q.y;
+      }
+      L.ggamma[c] += s2;
+      L.gbeta[c] += s1;
+    }
+  }
+  const int r0 = blockIdx.x * RB, cnt = min(RB, B - r0);
+  float* dy = reinterpret_cast<float*>(ws + L.dy_off);
+  const float* X = reinterpret_cast<const float*>(ws + L.z_off);  // xhat
+  const float* rstd = reinterpret_cast<const float*>(ws + L.stat_off);
+  bf16* img = reinterpret_cast<bf16*>(ws + L.dz_off);
+  for (int i = wid; i < cnt; i += BNT / 64) {
+    const long o = (long)(r0 + i) * N;
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = lane; c < N; c += 64) {
+      const float g = dy[o + c] * L.gamma[c];
+      s1 += g;
+      s2 += g * X[o + c];
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      s1 += __shfl_xor(s1, off);
+      s2 += __shfl_xor(s2, off);
+    }
+    const float m1 = s1 / (float)N, m2 = s2 / (float)N, rs = rstd[r0 + i];
+    for (int c = lane; c < L.S_z; c += 64) {
+      float dz = 0.f;
+      if (c < N) {
+        dz = rs * (dy[o + c] * L.gamma[c] - m1 - X[o + c] * m2);
+        dy[o + c] = dz;
+      }
+      img[(long)(r0 + i) * L.S_z + c] = (bf16)dz;
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  float* dbp = reinterpret_cast<float*>(ws + L.dbp_off);
+  for (int c = tid; c < N; c += BNT) {
+    float sum = 0.f;
+    for (int i = 0; i < cnt; ++i) sum += dy[(long)(r0 + i) * N + c];
+    dbp[(long)blockIdx.x * N + c] = sum;
   }
 }
 
@@ -631,7 +737,10 @@ headb_bwd_kernel(BArgs a, int l, char* __restrict__ ws, const float* __restrict_
     }
     const BLayer& P = a.L[l - 1];  // P.out == K
     float mean = 0.f, rstd = 1.f, s = 1.f, t = 0.f;
-    if (P.bn && kv) {
+    if (P.bn == 3 && kv) {  // LayerNorm: Z holds xhat already (mean 0, rstd 1 below)
+      s = P.gamma[k];
+      t = P.beta[k];
+    } else if (P.bn && kv) {
       const F2 st = reinterpret_cast<const F2*>(ws + P.stat_off)[k];
       mean = st.x;
       rstd = st.y;
@@ -808,7 +917,7 @@ static bool bplan(int nl, const int* dims, const int* flags, const float* drops,
       L.part_off = off;
       off = al256(off + 8 * R * N);
       L.stat_off = off;
-      off = al256(off + 8 * N);
+      off = al256(off + (L.bn == 3 ? 4 * Bl : 8 * N));  // LayerNorm: fp32 [B] per-row rstd
       L.dy_off = off;
       off = al256(off + 4 * Bl * N);
       L.part2_off = off;
@@ -873,6 +982,9 @@ int headb_fwd(int nl, const int* dims, const int* flags, const float* drops, con
     if (vx && vw) launch_fwd_layer(headb_fwd_kernel<true, true>, p, l, x, ldx, rng, ws, st);
     else if (vw) launch_fwd_layer(headb_fwd_kernel<false, true>, p, l, x, ldx, rng, ws, st);
     else launch_fwd_layer(headb_fwd_kernel<false, false>, p, l, x, ldx, rng, ws, st);
+    if (p.a.L[l].bn == 3)
+      hipLaunchKernelGGL(headb_ln_fwd_kernel, dim3((B + BNT / 64 - 1) / (BNT / 64)), dim3(BNT), 0,
+                         st, p.a, l, (char*)ws);
   }
   hipLaunchKernelGGL(headb_loss_kernel, dim3(1), dim3(LOSS_NT), 0, st, p.a, y, out, loss, pred,
                      rng, (char*)ws);
@@ -906,8 +1018,11 @@ int headb_bwd(int nl, const int* dims, const int* flags, const float* drops, con
     if (l < nl - 1 && L.bn) {
       unsigned g = (unsigned)p.a.nrb;
       const RedJob rj = take(p.a.nrb, g);
-      hipLaunchKernelGGL(headb_bn_bwd_kernel, dim3(g), dim3(BNT), 20 * L.out, st, p.a, l,
-                         (char*)ws, rj);
+      if (L.bn == 3)
+        hipLaunchKernelGGL(headb_ln_bwd_kernel, dim3(g), dim3(BNT), 0, st, p.a, l, (char*)ws, rj);
+      else
+        hipLaunchKernelGGL(headb_bn_bwd_kernel, dim3(g), dim3(BNT), 20 * L.out, st, p.a, l,
+                           (char*)ws, rj);
     }
     const int nkb = (L.in + TB - 1) / TB;
     const int nA = (l > 0 || dx) ? p.a.nrb * nkb : 0;

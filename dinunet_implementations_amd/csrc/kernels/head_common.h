@@ -44,6 +44,51 @@ __device__ __forceinline__ float colsum4(float v) {
   return v;
 }
 
+// ---- LayerNorm (norm mode 3) arithmetic shared by mlp_head.hip and head_rep.hip -----------------
+// Both kernels reduce in ONE order with pinned roundings (explicit fma / unfused multiplies), so
+// the one-launch and the three-launch heads agree bitwise:
+//  * along a row: per 16-column tile a butterfly over the tile's 16 lanes (lane & 15 = column in
+//    the tile, the MFMA accumulator layout), then the tiles added in tile order;
+//  * down a column: rows 16 mt + 4 q + r, each q's rows added in (mt, r) order, then
+//    (q0 + q1) + (q2 + q3) (= a per-lane register sum followed by colsum4).
+// a * b rounded to fp32 on its own.  The kernels are built with -ffp-contract=fast, which fuses a
+// multiply into a neighbouring add wherever the backend likes (and ignores contract pragmas), so
+// the product is taken by an instruction the optimiser cannot look into.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+__device__ __forceinline__ float tile16_sum(float v) {
+  v += __shfl_xor(v, 1);
+  v += __shfl_xor(v, 2);
+  v += __shfl_xor(v, 4);
+  v += __shfl_xor(v, 8);
+  return v;
+}
+
+// s + the four tile sums of one 64-column chunk (lane -> column of the chunk), in tile order
+__device__ __forceinline__ float ln_add_tiles(float s, float t) {
+  t = tile16_sum(t);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) s += __shfl(t, 16 * g);
+  return s;
+}
+
+__device__ __forceinline__ float ln_xhat(float z, float mean, float rstd) {
+  return mul_rn(z - mean, rstd);
+}
+
+__device__ __forceinline__ float ln_y(float gamma, float xhat, float beta) {
+  return __builtin_fmaf(gamma, xhat, beta);
+}
+
+// dz = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma
+__device__ __forceinline__ float ln_dz(float rstd, float g, float m1, float xhat, float m2) {
+  return mul_rn(rstd, __builtin_fmaf(-xhat, m2, g - m1));
+}
+
 // Fragment with lane i <- column c0 + (i & 15) and element j <- row k0 + 8 * (i >> 4) + j of a
 // row-major LDS image (row stride S elements): two hardware-transposed 4x16 reads.
 __device__ __forceinline__ bf16x8 tr_frag(const bf16* img, int S, int c0, int k0, int lane) {

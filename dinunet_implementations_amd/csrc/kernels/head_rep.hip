@@ -30,6 +30,12 @@
 // Numerics: the rounding points and reduction orders of mlp_head.hip (bf16 MFMA operands, fp32
 // accumulation, layer-0 K in four interleaved k-step groups summed in group order, the same
 // counter-hash dropout masks), so the one-launch and three-launch heads agree bitwise.
+//
+// Norm mode 3 (LayerNorm) is taken on layer 0, the ICA classifier's norm: a row's statistics span
+// the 16 waves' column tiles, so each wave leaves its tile's per-row sums in LDS (the dX reduction
+// buffer, idle until step 8), wave 0 adds them in tile order (lane = row) and every wave reads
+// back mean / rstd -- four workgroup barriers forward, two backward, xhat still in the owning
+// wave's registers.  Reduction orders and roundings are the shared ones of head_common.h.
 #include "head_common.h"
 #include <stdlib.h>
 
@@ -260,9 +266,16 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
   // ---- 2. layer 0: one output tile per wave; K in four interleaved k-step groups ------------
   const float p1 = L1.drop;
   const float inv1 = p1 > 0.f ? 1.f / (1.f - p1) : 1.f;
-  float xh[RMT][4];
+  float xh[RMT][4], z[RMT][4];
   float rstd = 0.f;
   unsigned relu_ok = 0xffu;  // bit 4 mt + r: post-ReLU output > 0
+  // LayerNorm scratch (in the dX reduction buffer, idle until step 8): per-tile row partials
+  // [2][RNW][RMP], then per row the mean / mean(g) [RMP], mean(g xhat) [RMP] and rstd [RMP]
+  float* lnA = reinterpret_cast<float*>(smem + a.t_red);
+  float* lnB = lnA + RNW * RMP;
+  float* lnm = lnB + RNW * RMP;
+  float* lnm2 = lnm + RMP;
+  float* lnr = lnm2 + RMP;
   if (t0v) {
     f32x4 acc[RMT], part[RMT];
 #pragma unroll
@@ -290,12 +303,13 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
     }
     const float* pp = reinterpret_cast<const float*>(smem + L0.p_lds);
     const float bias = pp[n];
-    float z[RMT][4];
 #pragma unroll
     for (int mt = 0; mt < RMT; ++mt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) z[mt][r] = acc[mt][r] + bias;
-    if (L0.bn) {
+    if (L0.bn == 3) {
+      // LayerNorm: below, with every wave at the barriers
+    } else if (L0.bn) {
       float s = 0.f;
 #pragma unroll
       for (int mt = 0; mt < RMT; ++mt)
@@ -332,6 +346,60 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
 #pragma unroll
         for (int r = 0; r < 4; ++r) xh[mt][r] = 0.f;
     }
+  }
+  if (L0.bn == 3) {
+    // LayerNorm over layer 0's N0 columns: a row spans the waves' tiles, so each wave leaves its
+    // tile's row sums in LDS and wave 0 (lane = row) adds them in tile order -- the reduction
+    // order and the pinned arithmetic of head_common.h, bitwise the three-launch head's
+    const int nt0 = L0.Np / 16;
+    if (t0v) {
+#pragma unroll
+      for (int mt = 0; mt < RMT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float t = tile16_sum(cv ? z[mt][r] : 0.f);
+          if (ln == 0) lnA[wid * RMP + 16 * mt + 4 * q + r] = t;
+        }
+    }
+    rlds_barrier();
+    if (wid == 0 && lane < RMP) {
+      float s = 0.f;
+      for (int t = 0; t < nt0; ++t) s += lnA[t * RMP + lane];
+      lnm[lane] = s / (float)N0;
+    }
+    rlds_barrier();
+    if (t0v) {
+#pragma unroll
+      for (int mt = 0; mt < RMT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * mt + 4 * q + r;
+          const float dd = cv ? z[mt][r] - lnm[row] : 0.f;
+          const float t = tile16_sum(mul_rn(dd, dd));
+          if (ln == 0) lnA[wid * RMP + row] = t;
+        }
+    }
+    rlds_barrier();
+    if (wid == 0 && lane < RMP) {
+      float s = 0.f;
+      for (int t = 0; t < nt0; ++t) s += lnA[t * RMP + lane];
+      lnr[lane] = rsqrtf(s / (float)N0 + L0.eps);
+    }
+    rlds_barrier();
+    if (t0v) {
+      const float* pp = reinterpret_cast<const float*>(smem + L0.p_lds);
+      const float ga = pp[L0.Np + n], be = pp[2 * L0.Np + n];
+#pragma unroll
+      for (int mt = 0; mt < RMT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * mt + 4 * q + r;
+          xh[mt][r] = (row < B && cv) ? ln_xhat(z[mt][r], lnm[row], lnr[row]) : 0.f;
+          z[mt][r] = ln_y(ga, xh[mt][r], be);
+        }
+    }
+  }
+  if (t0v) {
     bf16* a1 = reinterpret_cast<bf16*>(smem + L1.a_lds);
 #pragma unroll
     for (int mt = 0; mt < RMT; ++mt)
@@ -650,7 +718,8 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
   }
   RSTAMP(6);
 
-  // ---- 7. dA0 = dZ1 W1 on this wave's layer-0 tile, ReLU / BatchNorm backward -> dZ0 ---------
+  // ---- 7. dA0 = dZ1 W1 on this wave's layer-0 tile, ReLU / norm backward -> dZ0 ---------------
+  float d[RMT][4];
   if (t0v) {
     const bf16* w1 = reinterpret_cast<const bf16*>(smem + L1.w_lds);
     const bf16* z1 = reinterpret_cast<const bf16*>(smem + L1.z_lds);
@@ -666,8 +735,6 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
         da[mt] = mfma16(zf, bq, da[mt]);
       }
     }
-    const float* pp = reinterpret_cast<const float*>(smem + L0.p_lds);
-    float d[RMT][4];
 #pragma unroll
     for (int mt = 0; mt < RMT; ++mt)
 #pragma unroll
@@ -678,6 +745,64 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
         if (L0.relu && !((relu_ok >> (4 * mt + r)) & 1u)) t = 0.f;
         d[mt][r] = t;
       }
+  }
+  if (L0.bn == 3) {
+    // LayerNorm backward: the two row sums of g = dy gamma cross the waves' tiles through LDS as
+    // in the forward; d gamma / d beta / the bias gradient are column sums in the owning wave
+    const float* pp = reinterpret_cast<const float*>(smem + L0.p_lds);
+    const float ga = (t0v && cv) ? pp[L0.Np + n] : 0.f;
+    if (t0v) {
+#pragma unroll
+      for (int mt = 0; mt < RMT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * mt + 4 * q + r;
+          const float gv = mul_rn(d[mt][r], ga);
+          const float t1 = tile16_sum(gv);
+          const float t2 = tile16_sum(mul_rn(gv, xh[mt][r]));
+          if (ln == 0) {
+            lnA[wid * RMP + row] = t1;
+            lnB[wid * RMP + row] = t2;
+          }
+        }
+    }
+    rlds_barrier();
+    if (wid == 0 && lane < RMP) {
+      float s1 = 0.f, s2 = 0.f;
+      for (int t = 0; t < L0.Np / 16; ++t) {
+        s1 += lnA[t * RMP + lane];
+        s2 += lnB[t * RMP + lane];
+      }
+      lnm[lane] = s1 / (float)N0;
+      lnm2[lane] = s2 / (float)N0;
+    }
+    rlds_barrier();
+    if (t0v) {
+      float s1 = 0.f, s2 = 0.f, sb = 0.f;
+#pragma unroll
+      for (int mt = 0; mt < RMT; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * mt + 4 * q + r;
+          const float dy = d[mt][r];
+          s1 += dy;
+          s2 = __builtin_fmaf(dy, xh[mt][r], s2);
+          const float dzv = (row < B && cv)
+              ? ln_dz(lnr[row], mul_rn(dy, ga), lnm[row], xh[mt][r], lnm2[row]) : 0.f;
+          sb += dzv;
+          d[mt][r] = dzv;
+        }
+      s1 = colsum4(s1);
+      s2 = colsum4(s2);
+      sb = colsum4(sb);
+      if (lead && lane < 16 && cv) {
+        L0.ggamma[n] = pp[6 * L0.Np + n] + s2;
+        L0.gbeta[n] = pp[7 * L0.Np + n] + s1;
+        if (L0.b) L0.gb[n] = pp[5 * L0.Np + n] + sb;
+      }
+    }
+  } else if (t0v) {
+    const float* pp = reinterpret_cast<const float*>(smem + L0.p_lds);
     if (L0.bn) {
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -712,6 +837,8 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
       sb = colsum4(sb);
       if (lead && lane < 16 && cv) L0.gb[n] = pp[5 * L0.Np + n] + sb;
     }
+  }
+  if (t0v) {
     bf16* z0 = reinterpret_cast<bf16*>(smem + L0.z_lds);
 #pragma unroll
     for (int mt = 0; mt < RMT; ++mt)
@@ -839,6 +966,9 @@ static bool rep_plan(int nl, const int* dims, const int* flags, const float* dro
     L.Kp = rup32(L.in);
     L.Np = rup32(L.out);
     L.bn = flags[l] & 3;
+    // norm mode 3 (LayerNorm) on layer 0 only (the ICA classifier): its row reduction crosses the
+    // 16 waves' column tiles through LDS; elsewhere the caller's three-launch path runs the head
+    if (L.bn == 3 && l > 0) return false;
     L.relu = (flags[l] >> 2) & 1;
     L.drop = drops ? drops[l] : 0.f;
     if (L.drop < 0.f || L.drop >= 1.f) return false;

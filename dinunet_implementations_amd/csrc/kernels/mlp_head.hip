@@ -3,7 +3,7 @@
 // comps/fs/__init__.py:54-57) in two launches forward and two backward (instead of ~40 kernels).
 //
 // A head is a chain of at most HMAXL layers, each
-//     [dropout on the input] -> Linear (+bias) -> [BatchNorm1d] -> [ReLU]
+//     [dropout on the input] -> Linear (+bias) -> [BatchNorm1d | LayerNorm] -> [ReLU]
 // ending in softmax cross-entropy (probabilities out) or log-softmax + NLL (log-probs out).
 // Batch <= 64: everything is latency / per-CU-bandwidth bound (one CU streams only ~50 GB/s),
 // so the launches are split by where the bytes are:
@@ -23,6 +23,19 @@
 // synchronisation.  Dropout masks come from a counter-based hash of (seed, layer, row, col); the
 // seed is a device word bumped by fwd1, so a captured HIP graph draws fresh masks on every replay,
 // and the backward regenerates the mask from the seed saved in the workspace.
+//
+// Norm mode 3 (flags & 3): LayerNorm over the layer's `out` valid features, eps in bnp[2 l],
+// gamma / beta and their gradients in the BatchNorm pointer slots, no running state; the same
+// math in training and evaluation.  The reduction runs along a ROW, which a wave's 16-column
+// tile does not hold, so a LayerNorm layer's GEMM epilogue parks the fp32 pre-norm z (bias
+// included) in the layer's xhat workspace and the single workgroup of fwd1 normalises it, one
+// wave per row (ln_fwd_stage: after the fwd0 kernel boundary for layer 0, after a workgroup
+// barrier for the narrow layers), writing xhat back in place and (mean, rstd) per row.  The
+// backward mirrors it: the dA epilogue parks fp32 dy, ln_bwd_stage takes the two row sums
+// (wave per row, dz = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma) and then the column
+// sums d gamma, d beta and the (real) gradient of a bias ahead of the norm, a wave per 16-column
+// tile.  Every reduction has a fixed order (head_common.h, shared with head_rep.hip so the
+// one-launch head agrees bitwise): two runs are bitwise equal.
 #include "head_common.h"
 
 namespace {
@@ -45,7 +58,8 @@ struct HLayer {
   float* ggamma;
   float* gbeta;
   int in, out;
-  int bn;    // 0 none, 1 batch statistics always, 2 batch stats + running update (train) / running (eval)
+  int bn;    // 0 none, 1 batch statistics always, 2 batch stats + running update (train) / running (eval),
+             // 3 LayerNorm over the out features (row statistics; gamma / beta as for BatchNorm)
   int relu;
   float drop;  // dropout probability applied to this layer's INPUT (training only)
   float eps, momentum;
@@ -53,6 +67,8 @@ struct HLayer {
   int S_z;   // row stride of the output-gradient image                = rup32(out) + 8
   int Np;    // rup32(out)
   long a_off, xhat_off, rstd_off, dz_off;  // byte offsets into the workspace
+  // (LayerNorm: xhat holds the pre-norm z until the row pass; rstd is [2][Mp] per-ROW mean | rstd)
+  long dy_off, dzf_off;  // LayerNorm backward: fp32 [Mp][Np] dy (norm output grad) and dz
   long st_off;  // stash of the bias / BatchNorm grads [gb | ggamma | gbeta] (fused fwd+bwd1)
 };
 
@@ -154,7 +170,7 @@ __device__ __forceinline__ ColP load_colp(const HLayer& L, int n, bool train) {
   ColP c{0.f, 1.f, 0.f, 0.f, 1.f};
   const int i = n < L.out ? n : 0;
   if (L.b) c.bias = L.b[i];
-  if (L.bn) {
+  if (L.bn == 1 || L.bn == 2) {
     c.gamma = L.gamma[i];
     c.beta = L.beta[i];
     if (L.bn == 2) {
@@ -185,6 +201,17 @@ __device__ __forceinline__ void fwd_epilogue(const HArgs& a, int l, const f32x4 
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) z[mt][r] = acc[mt][r] + bias;
+  if (L.bn == 3) {  // LayerNorm: fp32 pre-norm z for the row pass (ln_fwd_stage), pad zeroed
+    float* zws = reinterpret_cast<float*>(ws + L.xhat_off);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * mt + 4 * (lane >> 4) + r;
+        zws[row * L.Np + n] = (row < B && cv) ? z[mt][r] : 0.f;
+      }
+    return;
+  }
   if (L.bn) {
     float mean, rstd;
     if (train || L.bn == 1) {
@@ -248,6 +275,138 @@ __device__ __forceinline__ void fwd_epilogue(const HArgs& a, int l, const f32x4 
         wnext[row * Sn + n] = bv;
       }
     }
+}
+
+// LayerNorm row pass of layer l (not the last), run by one whole workgroup of NT threads once the
+// layer's pre-norm z is complete in the workspace: one wave per row, (mean, biased var) over the
+// N valid columns in fp32 (two passes; the row order of head_common.h: tile butterflies, tiles in
+// order), xhat back in place, y = gamma xhat + beta -> ReLU -> the next layer's dropout -> bf16
+// into the LDS image `nxt` and the workspace image.  Rows >= B and columns >= N come out zero.
+template <int NT>
+__device__ __forceinline__ void ln_fwd_stage(const HArgs& a, int l, int Mp, uint64_t seed,
+                                             char* __restrict__ ws, bf16* nxt) {
+  const HLayer& L = a.L[l];
+  const HLayer& Ln = a.L[l + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int N = L.out, Np = L.Np, B = a.B, Sn = Ln.S_a;
+  const bool train = a.train != 0;
+  const float pn = train ? Ln.drop : 0.f;
+  const float invn = pn > 0.f ? 1.f / (1.f - pn) : 1.f;
+  float* zx = reinterpret_cast<float*>(ws + L.xhat_off);
+  float* stat = reinterpret_cast<float*>(ws + L.rstd_off);
+  bf16* wnext = reinterpret_cast<bf16*>(ws + Ln.a_off);
+  for (int row = wid; row < Mp; row += NT / 64) {
+    float* zr = zx + row * Np;
+    float mean = 0.f, rstd = 0.f;
+    if (row < B) {  // (wave-uniform)
+      float s = 0.f;
+      for (int c0 = 0; c0 < Np; c0 += 64) {
+        const int c = c0 + lane;
+        s = ln_add_tiles(s, c < N ? zr[c] : 0.f);
+      }
+      mean = s / (float)N;
+      float v = 0.f;
+      for (int c0 = 0; c0 < Np; c0 += 64) {
+        const int c = c0 + lane;
+        const float d = c < N ? zr[c] - mean : 0.f;
+        v = ln_add_tiles(v, mul_rn(d, d));
+      }
+      rstd = rsqrtf(v / (float)N + L.eps);
+    }
+    for (int c = lane; c < Np; c += 64) {
+      const bool ok = row < B && c < N;
+      const int cc = c < N ? c : 0;
+      const float xh = ok ? ln_xhat(zr[c], mean, rstd) : 0.f;
+      if (train) zr[c] = xh;
+      float v = ok ? ln_y(L.gamma[cc], xh, L.beta[cc]) : 0.f;
+      if (L.relu) v = fmaxf(v, 0.f);
+      if (pn > 0.f && v != 0.f) v = hkeep(seed, l + 1, row, c, N, pn) ? v * invn : 0.f;
+      const bf16 bv = (bf16)v;
+      if (nxt) nxt[row * Sn + c] = bv;
+      wnext[row * Sn + c] = bv;
+    }
+    if (train && lane == 0) {
+      stat[row] = mean;
+      stat[Mp + row] = rstd;
+    }
+  }
+}
+
+// LayerNorm backward of layer P = l - 1 from its fp32 dy in the workspace (run by one whole
+// workgroup): row pass (wave per row) dz = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma,
+// into the bf16 LDS image `dzn`, the workspace image and an fp32 copy; then, after a barrier, the
+// column pass (wave per 16-column tile, the column order of head_common.h): d gamma = sum dy xhat,
+// d beta = sum dy and the bias gradient = sum dz.  stash: write the sums (fused forward), else
+// accumulate into .grad.
+template <int NT>
+__device__ __forceinline__ void ln_bwd_stage(const HArgs& a, int lp, int Mp, int stash,
+                                             char* __restrict__ ws, bf16* dzn) {
+  const HLayer& P = a.L[lp];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int N = P.out, Np = P.Np, B = a.B, Sz = P.S_z;
+  const float* dy = reinterpret_cast<const float*>(ws + P.dy_off);
+  const float* xh = reinterpret_cast<const float*>(ws + P.xhat_off);
+  const float* stat = reinterpret_cast<const float*>(ws + P.rstd_off);
+  float* dzf = reinterpret_cast<float*>(ws + P.dzf_off);
+  bf16* wdz = reinterpret_cast<bf16*>(ws + P.dz_off);
+  for (int row = wid; row < Mp; row += NT / 64) {
+    float m1 = 0.f, m2 = 0.f, rstd = 0.f;
+    if (row < B) {  // (wave-uniform)
+      float s1 = 0.f, s2 = 0.f;
+      for (int c0 = 0; c0 < Np; c0 += 64) {
+        const int c = c0 + lane;
+        const float g = c < N ? mul_rn(dy[row * Np + c], P.gamma[c]) : 0.f;
+        s1 = ln_add_tiles(s1, g);
+        s2 = ln_add_tiles(s2, c < N ? mul_rn(g, xh[row * Np + c]) : 0.f);
+      }
+      m1 = s1 / (float)N;
+      m2 = s2 / (float)N;
+      rstd = stat[Mp + row];
+    }
+    for (int c = lane; c < Np; c += 64) {
+      const bool ok = row < B && c < N;
+      const int cc = c < N ? c : 0;
+      const float g = mul_rn(dy[row * Np + c], P.gamma[cc]);
+      const float v = ok ? ln_dz(rstd, g, m1, xh[row * Np + c], m2) : 0.f;
+      dzf[row * Np + c] = v;
+      const bf16 bv = (bf16)v;
+      dzn[row * Sz + c] = bv;
+      wdz[row * Sz + c] = bv;
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  float* const st = reinterpret_cast<float*>(ws + P.st_off);
+  // (a wave per 16-column tile, lane -> column lane & 15 and row group q = lane >> 4, as the MFMA
+  // accumulators of the tile would lie; rows >= B hold zeros in all three images)
+  for (int t = wid; t < Np / 16; t += NT / 64) {
+    const int c = 16 * t + (lane & 15), q = lane >> 4;
+    float sg = 0.f, sb = 0.f, sz = 0.f;
+#pragma unroll 1
+    for (int mt = 0; mt < Mp / 16; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = (16 * mt + 4 * q + r) * Np + c;
+        const float d = dy[o];
+        sg = __builtin_fmaf(d, xh[o], sg);
+        sb += d;
+        sz += dzf[o];
+      }
+    sg = colsum4(sg);
+    sb = colsum4(sb);
+    sz = colsum4(sz);
+    if (lane < 16 && c < N) {
+      if (stash) {
+        if (P.gb) st[c] = sz;
+        st[N + c] = sg;
+        st[2 * N + c] = sb;
+      } else {
+        if (P.gb) P.gb[c] += sz;
+        P.ggamma[c] += sg;
+        P.gbeta[c] += sb;
+      }
+    }
+  }
 }
 
 // Copy a bf16 workspace image (rows x S elements, S % 8 == 0) into LDS, loads batched.
@@ -441,7 +600,9 @@ __device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const long long* _
     load_w(a.L[1], 16 * wid + (lane & 15), 0);
     cp1 = load_colp(a.L[1], 16 * wid + (lane & 15), train);
   }
-  if (a.nl >= 2) {
+  if (a.nl >= 2 && a.L[0].bn == 3) {
+    ln_fwd_stage<NT>(a, 0, Mp, seed, ws, cur);  // layer 0's LayerNorm: fwd0 left the pre-norm z
+  } else if (a.nl >= 2) {
     ws_to_lds<NT>(cur, ws + a.L[1].a_off, Mp * a.L[1].S_a, tid);
   } else {
     const float* src = reinterpret_cast<const float*>(ws + a.logit_off);
@@ -477,6 +638,11 @@ __device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const long long* _
         }
       }
       fwd_epilogue<MT>(a, l, acc, n, lane, seed, ws, nxt, logit, cp);
+    }
+    if (L.bn == 3) {  // every tile's pre-norm z is in the workspace: the row pass
+      __threadfence_block();
+      __syncthreads();
+      ln_fwd_stage<NT>(a, l, Mp, seed, ws, nxt);
     }
     __syncthreads();
     HSTAMP(4 + l);
@@ -608,6 +774,9 @@ __device__ __forceinline__ void bwd1_body(const HArgs& a, char* __restrict__ ws,
     float* const gbw = stash ? st : P.gb;
     float* const ggw = stash ? st + P.out : P.ggamma;
     float* const gbew = stash ? st + 2 * P.out : P.gbeta;
+    const bool pbn = P.bn == 1 || P.bn == 2;  // BatchNorm (column statistics) below
+    const bool pln = P.bn == 3;               // LayerNorm: dy parked, ln_bwd_stage after the tiles
+    float* const dyw = reinterpret_cast<float*>(ws + P.dy_off);
 
     // Everything a tile needs from global memory, requested in one go (clamped addresses, no
     // use until the MFMAs / epilogue): weight columns of the first CB k-steps, the saved
@@ -631,7 +800,7 @@ __device__ __forceinline__ void bwd1_body(const HArgs& a, char* __restrict__ ws,
     const int kk_ = 16 * (t) + (lane & 15);                                     \
     const int kc_ = kk_ < K ? kk_ : 0;                                          \
     HB1_LOAD_W(w, 0, kk_)                                                       \
-    if (P.bn) {                                                                 \
+    if (pbn) {                                                                  \
       _Pragma("unroll") for (int mt = 0; mt < MT; ++mt)                         \
       _Pragma("unroll") for (int r = 0; r < 4; ++r)                             \
         xh[mt][r] = xhat_ws[(16 * mt + 4 * (lane >> 4) + r) * P.Np + kc_];      \
@@ -640,7 +809,7 @@ __device__ __forceinline__ void bwd1_body(const HArgs& a, char* __restrict__ ws,
       gg = stash ? 0.f : P.ggamma[kc_];                                         \
       gbe = stash ? 0.f : P.gbeta[kc_];                                         \
     }                                                                           \
-    if (P.gb) gbv = stash ? 0.f : P.gb[kc_];                                    \
+    if (P.gb && !pln) gbv = stash ? 0.f : P.gb[kc_];                            \
   } while (0)
     auto load_wc = [&](int nb, int kk) { HB1_LOAD_W(wc, nb, kk) };
     auto prefetch = [&](int t) { HB1_PREFETCH(t, wc, xhp, rsp, gap, ggo, gbeo, gbo); };
@@ -697,7 +866,15 @@ __device__ __forceinline__ void bwd1_body(const HArgs& a, char* __restrict__ ws,
           if (P.relu && !((float)abuf[row * Sa + kk] > 0.f)) v = 0.f;
           d[mt][r] = v;
         }
-      if (P.bn) {
+      if (pln) {  // (kk < rup32(K) == P.Np: the pad columns carry zeros)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            dyw[(16 * mt + 4 * (lane >> 4) + r) * P.Np + kk] = d[mt][r];
+        continue;
+      }
+      if (pbn) {
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
@@ -740,6 +917,11 @@ __device__ __forceinline__ void bwd1_body(const HArgs& a, char* __restrict__ ws,
           dzn[row * P.S_z + kk] = bv;
           wdz[row * P.S_z + kk] = bv;
         }
+    }
+    if (pln) {
+      __threadfence_block();
+      __syncthreads();
+      ln_bwd_stage<NT>(a, l - 1, Mp, stash, ws, dzn);
     }
     __syncthreads();
     HSTAMP(17 + (a.nl - 1 - l));
@@ -945,6 +1127,7 @@ static bool make_plan(int nl, const int* dims, const int* flags, const float* dr
     L.out = dims[l + 1];
     if (L.in < 1 || L.out < 1 || L.in > 2048 || L.out > 2048) return false;
     L.bn = flags[l] & 3;
+    if (L.bn == 3 && l == nl - 1) return false;  // the logits come straight out of a Linear
     L.relu = (flags[l] >> 2) & 1;
     L.drop = drops ? drops[l] : 0.f;
     if (L.drop < 0.f || L.drop >= 1.f) return false;
@@ -976,7 +1159,13 @@ static bool make_plan(int nl, const int* dims, const int* flags, const float* dr
     L.xhat_off = off;
     if (L.bn) off = al256(off + 4L * Mp * L.Np);
     L.rstd_off = off;
-    if (L.bn) off = al256(off + 4L * L.Np);
+    if (L.bn) off = al256(off + 4L * (L.bn == 3 ? 2 * Mp : L.Np));
+    L.dy_off = L.dzf_off = off;
+    if (L.bn == 3) {
+      off = al256(off + 4L * Mp * L.Np);
+      L.dzf_off = off;
+      off = al256(off + 4L * Mp * L.Np);
+    }
     L.dz_off = off;
     off = al256(off + 2L * Mp * L.S_z);
     L.st_off = off;
@@ -1084,7 +1273,8 @@ DN_API int dn_head_set_stamps(void* p) {
 // {input image byte offset, its row stride, output-gradient image byte offset, its row stride}
 // (bf16 images, rows = batch; used to hand rank-dAD its (A, Delta) pairs).  DN_UNSUPPORTED if
 // the head does not fit the fused kernels.
-// Per layer: dims[l] -> dims[l+1]; flags[l] = bn (0 none / 1 batch stats / 2 running) | relu << 2.
+// Per layer: dims[l] -> dims[l+1]; flags[l] = norm (0 none / 1 BatchNorm batch stats / 2 BatchNorm
+// running / 3 LayerNorm) | relu << 2.
 DN_API int dn_head_layout(int nl, const int* dims, const int* flags, int B, long* out) {
   if (B > 64) return headb_layout(nl, dims, flags, B, out);
   Plan p;

@@ -33,8 +33,8 @@ class MSANNet(nn.Module):
         if norm_layer not in ("batch", "layer"):
             raise ValueError(f"norm_layer {norm_layer!r}: expected 'batch' or 'layer'")
         for i, h in enumerate(self.hidden_sizes):
-            # "layer": the optional LayerNorm on its gfx950 kernels (ops.layernorm) in place of
-            # the reference's BatchNorm1d
+            # "layer": the optional LayerNorm in place of the reference's BatchNorm1d, fused into
+            # the head kernels as norm mode 3 (ops.head)
             norm = (nn.BatchNorm1d(h, track_running_stats=False) if norm_layer == "batch"
                     else ops.LayerNorm(h))
             block = [nn.Linear(d, h, bias=False), norm, nn.ReLU()]

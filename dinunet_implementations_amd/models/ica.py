@@ -144,8 +144,8 @@ class ICALstm(nn.Module):
         self.lstm = LSTM(input_size=input_size, hidden_size=hidden_size,
                          bidirectional=bidirectional, num_layers=num_layers)
         # norm_layer "batch": the reference's BatchNorm1d (fused head kernels); "layer": the
-        # optional LayerNorm on its own gfx950 kernels (ops.layernorm; the head then runs
-        # module by module)
+        # optional LayerNorm, fused into the same head kernels as norm mode 3 (ops.head; no
+        # coupling across the batch, so replicas of a site reproduce the one-GPU gradient)
         if norm_layer not in ("batch", "layer"):
             raise ValueError(f"norm_layer {norm_layer!r}: expected 'batch' or 'layer'")
         self.classifier = nn.Sequential(

@@ -14,6 +14,17 @@ what the modules would compute (parameters, BN eps/momentum/mode, dropout placem
 kernels do not cover (> 16 classes, layers wider than 2048, unknown modules) runs the modules +
 the loss op.
 
+``norm_layer="layer"`` heads are fused too: an ``nn.LayerNorm`` (``ops.LayerNorm`` included) after
+a ``Linear`` -- 1-D ``normalized_shape == out_features``, affine with a bias, ahead of the layer's
+ReLU -- is the kernels' norm mode 3 (``flags & 3``; eps in ``_bnp``, weight / bias and their
+gradient buffers in the BatchNorm pointer slots, no running state, the same math in training
+and evaluation, legal on one row).  Batches <= 64 normalise in the single-workgroup launches
+(a wave per row), larger batches with one extra launch per LayerNorm layer each way; a bias
+ahead of the norm gets its real gradient.  The one-launch replicated head (``head_rep.hip``)
+takes mode 3 on layer 0 (the ICA classifier), bitwise the three-launch result; a LayerNorm on a
+later layer of a hinted step runs the three-launch path.  Any other LayerNorm (no affine, no
+bias, after the ReLU, N-D shape) runs the modules.
+
 Batches above 64 rows run ``csrc/kernels/head_big.hip`` behind the same C entry points: one
 launch per layer forward (row blocks x 64-column blocks, the previous layer's BatchNorm + ReLU and
 this layer's dropout applied while staging the input tile) + one loss launch, one launch per
@@ -119,7 +130,7 @@ class _Layer:
 
     def __init__(self, linear: nn.Linear, drop: float):
         self.linear = linear
-        self.bn: Optional[nn.BatchNorm1d] = None
+        self.bn: Optional[nn.Module] = None  # the layer's norm: BatchNorm1d or LayerNorm
         self.relu = False
         self.drop = drop
 
@@ -147,6 +158,14 @@ class HeadSpec:
                     self.ok = False
                 else:
                     L.bn = m
+            elif isinstance(m, nn.LayerNorm):
+                L = self.layers[-1] if self.layers else None
+                if (L is None or L.bn is not None or L.relu or not m.elementwise_affine
+                        or m.bias is None or m.weight is None
+                        or tuple(m.normalized_shape) != (L.linear.out_features,)):
+                    self.ok = False
+                else:
+                    L.bn = m
             elif isinstance(m, nn.ReLU):
                 if not self.layers or self.layers[-1].relu:
                     self.ok = False
@@ -170,7 +189,10 @@ class HeadSpec:
         self._drops = (ctypes.c_float * n)(*[L.drop for L in self.layers])
         bnp = []
         for L in self.layers:
-            bnp += [L.bn.eps, L.bn.momentum or 0.0] if L.bn is not None else [1e-5, 0.1]
+            if L.bn is None:
+                bnp += [1e-5, 0.1]
+            else:  # (LayerNorm has no momentum: the kernels ignore the slot in mode 3)
+                bnp += [L.bn.eps, getattr(L.bn, "momentum", None) or 0.0]
         self._bnp = (ctypes.c_float * (2 * n))(*bnp)
         self._layout = {}
         self._rng: Optional[Tensor] = None
@@ -182,6 +204,8 @@ class HeadSpec:
     def _bn_mode(L: _Layer) -> int:
         if L.bn is None:
             return 0
+        if isinstance(L.bn, nn.LayerNorm):
+            return 3
         return 2 if L.bn.track_running_stats and L.bn.running_mean is not None else 1
 
     # ---- parameters / pointers --------------------------------------------------------------
@@ -216,7 +240,7 @@ class HeadSpec:
                 raise RuntimeError("fused head on GPU needs the gfx950 kernel library")
             return False
         B = x.shape[0]
-        if B < 2 and any(self._bn_mode(L) == 1 or (L.bn is not None and self.training)
+        if B < 2 and any(self._bn_mode(L) == 1 or (self._bn_mode(L) == 2 and self.training)
                          for L in self.layers):
             return False  # BatchNorm on one sample: let the modules raise like torch does
         if any(p.dtype != torch.float32 or not p.is_contiguous() for p in self.params()):

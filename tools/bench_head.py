@@ -1,5 +1,14 @@
 #!/usr/bin/env python3
-"""Fused MLP head fwd / bwd latency (CUDA events), ICA classifier and FS network shapes."""
+"""Fused MLP head fwd / bwd latency (CUDA events), ICA classifier and FS network shapes.
+
+``--step`` times one whole training step of the ICA classifier head (forward + loss + backward
+with the step's d-loss hint, as runtime.step runs it) per batch size in ``--batches``, with the
+norm chosen by ``--norm batch|layer``: eager wall time per step and GPU time per step from a
+replayed HIP graph of 20 steps, one JSON line per batch.  ``fused`` in the line says whether the
+fused head kernels took the head (false: the modules ran one by one).
+"""
+import argparse
+import json
 import os
 import sys
 
@@ -26,19 +35,69 @@ def t_us(fn, reps=50):
     return ts[len(ts) // 2]
 
 
+def _ica(norm, p):
+    from dinunet_implementations_amd import ops
+    nm = nn.BatchNorm1d(256) if norm == "batch" else ops.LayerNorm(256)  # as ICALstm builds it
+    return nn.Sequential(nn.Dropout(p), nn.Linear(384, 256), nm, nn.ReLU(), nn.Linear(256, 64),
+                         nn.ReLU(), nn.Linear(64, 2))
+
+
+def step_bench(norm, batches, p=0.25, n=20):
+    """One JSON line per batch: the hinted training step of the ICA head with ``norm``."""
+    from dinunet_implementations_amd.ops import head as H
+    dev = "cuda"
+    for B in batches:
+        torch.manual_seed(0)
+        mods = _ica(norm, p).to(dev).train()
+        spec = H.HeadSpec(list(mods))
+        x = torch.randn(B, 384, device=dev, requires_grad=True)
+        y = torch.randint(0, 2, (B,), device=dev)
+        one = torch.ones((), device=dev)
+
+        def step():
+            with H.loss_grad_hint(one):
+                _, loss, _ = H.head_loss(x, spec, y, log_out=False)
+            torch.autograd.backward(loss, one)
+
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        n0 = H.REP_LAUNCHES
+        with torch.cuda.stream(s):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(s)
+        one_launch = H.REP_LAUNCHES > n0
+        wall = t_us(step)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(n):
+                step()
+        gpu = t_us(g.replay, reps=20) / n
+        print(json.dumps({"head": "ica", "norm": norm, "B": B, "dropout": p,
+                          "fused": bool(spec.ok and spec.supported(x)), "one_launch": one_launch,
+                          "step_gpu_us": round(gpu, 2), "step_wall_us": round(wall, 2)}))
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--norm", choices=("batch", "layer"), default="batch",
+                    help="the ICA head's norm: BatchNorm1d (reference) or LayerNorm (norm_layer=layer)")
+    ap.add_argument("--step", action="store_true",
+                    help="time the hinted training step per batch size (JSON lines) and exit")
+    ap.add_argument("--batches", type=int, nargs="+", default=[32, 2048])
+    args = ap.parse_args()
+    if args.step:
+        step_bench(args.norm, args.batches)
+        return
     from dinunet_implementations_amd.models import MSANNet
     from dinunet_implementations_amd.ops.head import HeadSpec
     dev = "cuda"
     cases = [
-        ("ICA head B=32 p=0", nn.Sequential(nn.Dropout(0.0), nn.Linear(384, 256), nn.BatchNorm1d(256),
-                                         nn.ReLU(), nn.Linear(256, 64), nn.ReLU(), nn.Linear(64, 2)), 32, 384, False),
-        ("ICA head B=32", nn.Sequential(nn.Dropout(0.25), nn.Linear(384, 256), nn.BatchNorm1d(256),
-                                         nn.ReLU(), nn.Linear(256, 64), nn.ReLU(), nn.Linear(64, 2)), 32, 384, False),
-        ("ICA head B=64", nn.Sequential(nn.Dropout(0.25), nn.Linear(384, 256), nn.BatchNorm1d(256),
-                                         nn.ReLU(), nn.Linear(256, 64), nn.ReLU(), nn.Linear(64, 2)), 64, 384, False),
+        ("ICA head B=32 p=0", _ica(args.norm, 0.0), 32, 384, False),
+        ("ICA head B=32", _ica(args.norm, 0.25), 32, 384, False),
+        ("ICA head B=64", _ica(args.norm, 0.25), 64, 384, False),
     ]
-    fs = MSANNet(66, [256, 128, 64, 32], 2)
+    fs = MSANNet(66, [256, 128, 64, 32], 2, norm_layer=args.norm)
     cases.append(("FS MSANNet B=16", nn.Sequential(*[m for blk in fs.layers for m in blk], fs.fc_out), 16, 66, True))
     for name, mods, B, D, log_out in cases:
         mods = mods.to(dev).train()

@@ -74,6 +74,8 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     # collective plan for the xGMI mesh (README "Collective plan"): dSGD bucket size, RCCL
     # algorithm / protocol (None = RCCL's own choice), per-collective timeout
     "dsgd_bucket_mb": 4.0,
+    # global-norm gradient clipping in the fused Adam (ops.FusedAdam max_grad_norm): 0 = off
+    "max_grad_norm": 0,
     "rccl_algo": None,
     "rccl_proto": None,
     "collective_timeout_s": 1800,
@@ -267,6 +269,10 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if cfg.get("num_folds") is None and sr is not None:
         if len(sr) not in (2, 3) or abs(sum(sr) - 1.0) > 1e-6:
             raise ValueError(f"split_ratio must have 2-3 entries summing to 1, got {sr}")
+    mg = cfg.get("max_grad_norm", 0) or 0
+    if isinstance(mg, bool) or not isinstance(mg, (int, float)) or not (0 <= mg <= 3.4e38):
+        raise ValueError(f"max_grad_norm must be a number >= 0 (0 = off), got {mg!r}")
+    cfg["max_grad_norm"] = mg
     cfg["mode"] = str(cfg.get("mode", "train")).lower()
     cfg["metric_direction"] = cfg.get("metric_direction", "maximize")
     return cfg

@@ -5,18 +5,79 @@
 
 namespace {
 
+// ---------------------------------------------------------------------------------------------
+// Global-norm gradient clipping (FusedAdam max_grad_norm).  grad_sqnorm_kernel leaves CLIP_PARTS
+// fp64 partial sums of g^2 (a fixed grid, so every partial is rewritten by every launch and the
+// same data always gives the same bits); the Adam launch that follows sums them in the prologue of
+// every updating wave -- no finalize launch, no float atomics, no "last workgroup" ticket.
+constexpr int CLIP_PARTS = 256;  // one workgroup per CU; ~4 float4 per thread at 1 M elements
+struct ClipState {
+  double part[CLIP_PARTS];
+  float max_norm;  // threshold c (host-written; read here, so a captured graph follows it)
+  float norm;      // last G = grad_scale * ||g||_2
+  int skipped;     // updates skipped for a non-finite G
+  int pad;
+};
+
+__device__ __forceinline__ double wave_sum_f64(double x) {  // fixed butterfly: all lanes agree
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
+__global__ void __launch_bounds__(256)
+grad_sqnorm_kernel(const float* __restrict__ g, long n4, ClipState* __restrict__ cs) {
+  __shared__ double wsum[4];
+  double acc = 0.0;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc += (double)gg[e] * (double)gg[e];
+  }
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) cs->part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// Prologue of a clipped update (all 64 lanes of the wave active): the partials summed in one
+// fixed order, G = grad_scale * sqrt(sum), and torch.nn.utils.clip_grad_norm_'s coefficient folded
+// into the gradient scale, rounded to fp32 once.  G <= c gives grad_scale back exactly.  A
+// non-finite G sets skip; workgroup 0 records G and counts the skip.
+__device__ __forceinline__ float clip_coef(ClipState* __restrict__ cs, float grad_scale, bool& skip) {
+  const int l = threadIdx.x & 63;
+  const double s = wave_sum_f64((cs->part[l] + cs->part[l + 64]) +
+                                (cs->part[l + 128] + cs->part[l + 192]));
+  const double G = (double)grad_scale * sqrt(s);
+  const float Gf = (float)G;
+  skip = !(fabsf(Gf) <= 3.402823466e+38f);  // inf or NaN
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    cs->norm = Gf;
+    if (skip) cs->skipped += 1;
+  }
+  return (float)((double)grad_scale * fmin(1.0, (double)cs->max_norm / (G + 1e-6)));
+}
+
 // torch.optim.Adam semantics (L2 weight decay, no amsgrad):
 //   g += wd * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
 // grad_scale folds the dSGD mean (1/world) or loss scaling into the same pass.
+// CLIP: the gradient scale and the skip flag come from clip_coef (cs non-null).
+template <bool CLIP>
 __global__ void __launch_bounds__(256)
 adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
             float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
             float bc1, float inv_sqrt_bc2, float grad_scale, const int* __restrict__ tdev,
-            double b1d, double b2d, int tofs, long long* __restrict__ cursor) {
+            double b1d, double b2d, int tofs, long long* __restrict__ cursor,
+            ClipState* __restrict__ cs) {
   // the device-fed batch cursor (prologue.h) advances once per update; no workgroup of this
   // launch reads it
   if (cursor && blockIdx.x == 0 && threadIdx.x == 0) *cursor += 1;
+  if constexpr (CLIP) {
+    bool skip;
+    grad_scale = clip_coef(cs, grad_scale, skip);
+    if (skip) return;  // p, m, v untouched; the step number still advances
+  }
   if (tdev) {  // graph-replayable form: the step number lives on the device (adam_bump_kernel);
                // double math as on the host, so both forms round to the same fp32 corrections
     const double t = (double)(*tdev + tofs);  // tofs 0: the step prologue advanced it
@@ -193,11 +254,13 @@ __device__ __forceinline__ void record_step(const StepRecord& r, int cofs) {
 
 __global__ void __launch_bounds__(256) record_kernel(StepRecord r, int cofs) { record_step(r, cofs); }
 
+template <bool CLIP>
 __global__ void __launch_bounds__(256)
 adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                  float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
                  float grad_scale, const int* __restrict__ tdev, double b1d, double b2d, int update,
-                 int zero_grad, PackPlan pl, StepPrologue sp, int gofs, int ublocks, StepRecord rec) {
+                 int zero_grad, PackPlan pl, StepPrologue sp, int gofs, int ublocks, StepRecord rec,
+                 ClipState* __restrict__ cs) {
   // the step's train record (rec.out set): the LAST workgroup; the cursor was advanced by this
   // step's encoder GEMM, so it names the batch this step trained on
   if (rec.out && blockIdx.x == gridDim.x - 1) {
@@ -213,6 +276,11 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
     for (long i = (blockIdx.x - ublocks) * (long)blockDim.x + threadIdx.x; i < ng; i += stride)
       prologue_item(sp, i, c);  // sp.ug == 0: the zeroing rides in the update below
     return;
+  }
+  if constexpr (CLIP) {  // (launched with update set only)
+    bool skip;
+    grad_scale = clip_coef(cs, grad_scale, skip);
+    if (skip) update = 0;  // images from the unchanged parameters, gradient still zeroed
   }
   float bc1 = 1.f, inv_sqrt_bc2 = 1.f;
   if (update) {  // the encoder GEMM of this step advanced *tdev (prebumped form)
@@ -294,13 +362,27 @@ int grid_for(long n) {
 
 }  // namespace
 
+// The squared-norm partials of g for the clipped update that follows on the same stream.
+DN_API int dn_clip_parts() { return CLIP_PARTS; }
+DN_API long dn_clip_state_size() { return (long)sizeof(ClipState); }
+DN_API int dn_grad_sqnorm(const float* g, long n, void* clip, hipStream_t st) {
+  if (n <= 0 || n % 4 || !clip) return DN_BAD_SHAPE;
+  if (((uintptr_t)g & 15) || ((uintptr_t)clip & 7)) return DN_BAD_SHAPE;
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(CLIP_PARTS), dim3(256), 0, st, g, n / 4,
+                     reinterpret_cast<ClipState*>(clip));
+  return dn_launch_status();
+}
+
+// clip (a ClipState dn_grad_sqnorm filled for this gradient) non-null: the clipped update.
 DN_API int dn_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1,
                    float b2, float eps, float wd, float bc1, float inv_sqrt_bc2, float grad_scale,
-                   long long* cursor, hipStream_t st) {
+                   long long* cursor, void* clip, hipStream_t st) {
   if (n <= 0) return DN_OK;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, st, p, g, m, v, n, lr,
-                     b1, b2, eps, wd, bc1, inv_sqrt_bc2, grad_scale, (const int*)nullptr, 0.0, 0.0, 1, cursor);
+  hipLaunchKernelGGL(clip ? adam_kernel<true> : adam_kernel<false>, dim3(grid_for(n / 4 + 1)),
+                     dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, inv_sqrt_bc2,
+                     grad_scale, (const int*)nullptr, 0.0, 0.0, 1, cursor,
+                     reinterpret_cast<ClipState*>(clip));
   return dn_launch_status();
 }
 
@@ -308,12 +390,13 @@ DN_API int dn_adam(float* p, const float* g, float* m, float* v, long n, float l
 // HIP graph and replayed every step with the right bias corrections.  *tdev = completed steps.
 DN_API int dn_adam_dev(float* p, const float* g, float* m, float* v, long n, float lr, double b1,
                        double b2, float eps, float wd, float grad_scale, int* tdev, int prebumped,
-                       long long* cursor, hipStream_t st) {
+                       long long* cursor, void* clip, hipStream_t st) {
   if (n <= 0) return DN_OK;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, st, p, g, m, v, n, lr,
-                     (float)b1, (float)b2, eps, wd, 0.f, 0.f, grad_scale, (const int*)tdev, b1, b2, prebumped ? 0 : 1,
-                     cursor);
+  hipLaunchKernelGGL(clip ? adam_kernel<true> : adam_kernel<false>, dim3(grid_for(n / 4 + 1)),
+                     dim3(256), 0, st, p, g, m, v, n, lr, (float)b1, (float)b2, eps, wd, 0.f, 0.f,
+                     grad_scale, (const int*)tdev, b1, b2, prebumped ? 0 : 1, cursor,
+                     reinterpret_cast<ClipState*>(clip));
   if (!prebumped) hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, tdev);
   return dn_launch_status();
 }
@@ -327,8 +410,9 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
                         int HD, const void* gx, int gx_bf16, long row_elems, const long long* gy,
                         const long long* order, long nb, const long long* cursor, int B,
                         void* xb, long long* yd, long long* sd, int gofs, const void* record,
-                        hipStream_t st) {
+                        void* clip, hipStream_t st) {
   if (n <= 0 || n % 4 || cnt < 0 || cnt > PACK_SEGS) return DN_BAD_SHAPE;
+  if (clip && !update) return DN_BAD_SHAPE;  // the partials belong to an update's gradient
   StepRecord rec{};
   if (record && update) {
     rec = *reinterpret_cast<const StepRecord*>(record);
@@ -363,9 +447,10 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
   // rest start as the first retire)
   auto parts = [](long items) { return (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096); };
   const int ub = parts(n / 4), gb = sp.gx ? parts(sp.ux + sp.ny) : 0;
-  hipLaunchKernelGGL(adam_pack_kernel, dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, p, g,
-                     m, v, n, lr, (float)b1, (float)b2, eps, wd, grad_scale, tdev, b1, b2, update,
-                     zero_grad, pl, sp, gofs, ub, rec);
+  hipLaunchKernelGGL(clip ? adam_pack_kernel<true> : adam_pack_kernel<false>,
+                     dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, p, g, m, v, n, lr,
+                     (float)b1, (float)b2, eps, wd, grad_scale, tdev, b1, b2, update, zero_grad, pl,
+                     sp, gofs, ub, rec, reinterpret_cast<ClipState*>(clip));
   return dn_launch_status();
 }
 

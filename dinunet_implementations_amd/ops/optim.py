@@ -12,6 +12,7 @@ Semantics match ``torch.optim.Adam`` / ``torch.optim.SGD`` (checked against them
 from __future__ import annotations
 
 import math
+import os
 from typing import Dict, Iterable, List, Optional
 
 import torch
@@ -20,11 +21,12 @@ import torch.nn as nn
 from . import _lib
 
 _lib.register("dn_adam", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
-                          _lib.c_long] + [_lib.c_float] * 8 + [_lib.c_void_p, _lib.c_void_p])
+                          _lib.c_long] + [_lib.c_float] * 8 + [_lib.c_void_p] * 3)
 _lib.register("dn_adam_dev", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
                               _lib.c_long, _lib.c_float, _lib.c_double, _lib.c_double,
                               _lib.c_float, _lib.c_float, _lib.c_float, _lib.c_void_p,
-                              _lib.c_int, _lib.c_void_p, _lib.c_void_p])
+                              _lib.c_int, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p])
+_lib.register("dn_grad_sqnorm", [_lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_void_p])
 _lib.register("dn_step_gather", [_lib.c_void_p, _lib.c_int, _lib.c_long, _lib.c_void_p,
                                  _lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_int,
                                  _lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
@@ -46,7 +48,8 @@ _lib.register("dn_adam_pack", [_lib.c_void_p] * 4 + [_lib.c_long, _lib.c_float, 
                                _lib.c_int, _lib.c_int, _lib.c_int, _lib.c_void_p, _lib.c_int,
                                _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
                                _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
-                               _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p])
+                               _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
+                               _lib.c_void_p])
 _lib.register("dn_step_record", [_lib.c_void_p, _lib.c_int, _lib.c_void_p])
 
 
@@ -56,6 +59,9 @@ def ctypes_addr(obj) -> int:
 
 
 ALIGN = 4  # elements (16 bytes)
+
+# fp64 partial sums of optim.hip ClipState (checked against the library on a GPU)
+CLIP_PARTS = 256
 
 
 class FlatParams:
@@ -101,11 +107,41 @@ class FlatParams:
         return sum(p.numel() for p in ps)
 
 
+def _check_max_norm(value) -> float:
+    c = float(value)
+    if not (0.0 <= c <= 3.4e38):  # (an fp32 word on the device)
+        raise ValueError(f"max_grad_norm must be a finite fp32 number >= 0 (0 = off), got {value!r}")
+    return c
+
+
+def clip_coef(grad: torch.Tensor, grad_scale: float, max_norm: float):
+    """``(coef, G)`` of global-norm clipping as the kernels compute it (optim.hip clip_coef):
+    ``G = grad_scale * ||grad||_2`` from an fp64 sum of squares, ``coef = grad_scale * min(1,
+    max_norm / (G + 1e-6))`` rounded to fp32 once; ``G`` rounded to fp32 (non-finite: skip)."""
+    c = float(torch.tensor(float(max_norm), dtype=torch.float32))  # the device word
+    gs = float(torch.tensor(float(grad_scale), dtype=torch.float32))
+    Gd = gs * math.sqrt(float(grad.double().square().sum())) if grad.numel() else 0.0
+    G = float(torch.tensor(Gd, dtype=torch.float32))
+    coef = gs * min(1.0, c / (Gd + 1e-6)) if math.isfinite(Gd) else float("nan")
+    return float(torch.tensor(coef, dtype=torch.float32)), G
+
+
 class FusedAdam:
-    """``torch.optim.Adam`` on a :class:`FlatParams` buffer in one kernel launch per step."""
+    """``torch.optim.Adam`` on a :class:`FlatParams` buffer in one kernel launch per step.
+
+    ``max_grad_norm = c > 0``: global-norm clipping on the device, the same on every step form.
+    ``G = grad_scale * ||flat.grad||_2`` (fp64 sum of squares in a fixed order) and the gradient
+    scale becomes ``grad_scale * min(1, c / (G + 1e-6))`` (``torch.nn.utils.clip_grad_norm_``),
+    rounded to fp32 once, so ``G <= c`` leaves the update bit-identical to the unclipped one.  A
+    non-finite ``G`` skips the update -- parameters and both moments untouched, ``skipped_steps``
+    advanced -- while everything else the launch does (gradient zeroed, images rewritten, next
+    batch gathered, cursor and step number advanced) still happens.  ``None``: the
+    ``DINUNET_MAX_GRAD_NORM`` switch, else off; ``0``: off.  On / off is fixed here (it changes
+    what is launched); the threshold itself lives on the device and may change between replays of
+    a captured graph."""
 
     def __init__(self, flat: FlatParams, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0, max_grad_norm: Optional[float] = None):
         self.flat = flat
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.data)
@@ -114,6 +150,63 @@ class FusedAdam:
         self._tdev: Optional[torch.Tensor] = None  # device step counter (graph-captured steps)
         # device-fed batches (ops.DeviceSource): the update advances the source's cursor
         self.cursor: Optional[torch.Tensor] = None
+        if max_grad_norm is None:
+            env = os.environ.get("DINUNET_MAX_GRAD_NORM", "")
+            max_grad_norm = float(env) if env else 0.0
+        c = _check_max_norm(max_grad_norm)
+        # clip state (optim.hip ClipState): [CLIP_PARTS] fp64 partials, then the words
+        # {fp32 threshold, fp32 last norm, int32 skipped, pad}
+        self._clip: Optional[torch.Tensor] = None
+        self._max_grad_norm = c if c > 0 else None
+        if c > 0:
+            dev = flat.data.device
+            if dev.type == "cuda":
+                L = _lib.lib()
+                L.dn_clip_state_size.restype = _lib.c_long
+                if (int(L.dn_clip_parts()) != CLIP_PARTS
+                        or int(L.dn_clip_state_size()) != (CLIP_PARTS + 2) * 8):
+                    raise RuntimeError("clip state layout mismatch with the kernel library")
+            self._clip = torch.zeros(CLIP_PARTS + 2, dtype=torch.float64, device=dev)
+            self._clip_f = self._clip[CLIP_PARTS:].view(torch.float32)
+            self._clip_i = self._clip[CLIP_PARTS:].view(torch.int32)
+            self._clip_f[0] = c
+
+    # global-norm clipping ----------------------------------------------------------------------
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value: Optional[float]):
+        on = value is not None and _check_max_norm(value) > 0
+        if on != (self._clip is not None):
+            raise ValueError("FusedAdam.max_grad_norm: clipping is switched on or off when the "
+                             "optimizer is built (it changes what is launched)")
+        if not on:
+            return
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            # the write would become a graph node that resets the threshold at every replay
+            raise RuntimeError("FusedAdam.max_grad_norm set inside a HIP graph capture")
+        self._max_grad_norm = float(value)
+        self._clip_f[0] = float(value)
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """fp32 [] on the optimizer's device: ``G`` of the last update (None with clipping off)."""
+        return None if self._clip is None else self._clip_f[1]
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """int32 [] on the optimizer's device: updates skipped for a non-finite ``G``."""
+        return None if self._clip is None else self._clip_i[2]
+
+    def _sqnorm(self) -> Optional[int]:
+        """Launch the squared-norm partials of the gradient; the clip state for the Adam launch."""
+        if self._clip is None:
+            return None
+        _lib.call("dn_grad_sqnorm", self.flat.grad.data_ptr(), self.flat.grad.numel(),
+                  self._clip.data_ptr(), _lib.stream())
+        return self._clip.data_ptr()
 
     def zero_grad(self, set_to_none: bool = False):
         self.flat.zero_grad()
@@ -125,11 +218,18 @@ class FusedAdam:
         bc2 = 1 - b2 ** self.step_count
         d = self.flat.data
         if d.is_cuda:
+            clip = self._sqnorm()
             _lib.call("dn_adam", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
                       self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
                       self.weight_decay, bc1, 1.0 / math.sqrt(bc2), grad_scale,
-                      _lib.ptr(self.cursor), _lib.stream())
+                      _lib.ptr(self.cursor), clip, _lib.stream())
             return
+        if self._clip is not None:
+            grad_scale, G = clip_coef(self.flat.grad, grad_scale, self._max_grad_norm)
+            self._clip_f[1] = G
+            if not math.isfinite(G):
+                self._clip_i[2] += 1
+                return
         g = self.flat.grad * grad_scale
         if self.weight_decay:
             g = g + self.weight_decay * d
@@ -160,10 +260,11 @@ class FusedAdam:
         if self._tdev is None:
             self.sync_device_step()
         b1, b2 = self.betas
+        clip = self._sqnorm()
         _lib.call("dn_adam_dev", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
                   self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
                   self.weight_decay, grad_scale, self._tdev.data_ptr(), int(prebumped),
-                  _lib.ptr(self.cursor), _lib.stream())
+                  _lib.ptr(self.cursor), clip, _lib.stream())
 
     # Adam that also emits the next step's operands (optim.hip adam_pack_kernel) ------------------
     def attach_pack(self, pack, src=None, xb: Optional[torch.Tensor] = None,
@@ -209,11 +310,13 @@ class FusedAdam:
                   xb.data_ptr() if copy_x else None, yd.data_ptr(), _lib.ptr(sd)]
         else:
             gx = [None, 0, 0, None, None, 1, None, 0, None, None, None]
+        clip = self._sqnorm() if update else None
         _lib.call("dn_adam_pack", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
                   self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
                   self.weight_decay, grad_scale, self._tdev.data_ptr(), int(update), 1,
                   ctypes_addr(tab), cnt, pack.I, pack.Hd, pack.HD, *gx, int(gofs),
-                  ctypes_addr(record) if (record is not None and update) else None, _lib.stream())
+                  ctypes_addr(record) if (record is not None and update) else None, clip,
+                  _lib.stream())
 
     def device_step(self) -> torch.Tensor:
         """The device step counter (int32[1]) the graph-captured update reads; a step prologue
@@ -223,9 +326,13 @@ class FusedAdam:
         return self._tdev
 
     def state_dict(self) -> Dict:
-        return {"lr": self.lr, "betas": self.betas, "eps": self.eps,
-                "weight_decay": self.weight_decay, "step": self.step_count,
-                "exp_avg": self.exp_avg.detach().cpu(), "exp_avg_sq": self.exp_avg_sq.detach().cpu()}
+        sd = {"lr": self.lr, "betas": self.betas, "eps": self.eps,
+              "weight_decay": self.weight_decay, "step": self.step_count,
+              "exp_avg": self.exp_avg.detach().cpu(), "exp_avg_sq": self.exp_avg_sq.detach().cpu()}
+        if self._clip is not None:
+            sd["max_grad_norm"] = self._max_grad_norm
+            sd["skipped"] = int(self.skipped_steps.item())
+        return sd
 
     def load_state_dict(self, sd: Dict):
         self.lr = sd.get("lr", self.lr)
@@ -236,6 +343,11 @@ class FusedAdam:
         if "exp_avg" in sd:
             self.exp_avg.copy_(sd["exp_avg"].to(self.exp_avg.device))
             self.exp_avg_sq.copy_(sd["exp_avg_sq"].to(self.exp_avg_sq.device))
+        if self._clip is not None:  # (on / off stays as built; older checkpoints carry neither)
+            if sd.get("max_grad_norm"):
+                self.max_grad_norm = float(sd["max_grad_norm"])
+            if "skipped" in sd:
+                self._clip_i[2] = int(sd["skipped"])
 
 
 def step_prologue(x: torch.Tensor, xb: Optional[torch.Tensor], y: torch.Tensor,

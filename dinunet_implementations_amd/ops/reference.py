@@ -111,8 +111,17 @@ def log_softmax_nll(logits: Tensor, labels: Tensor):
 
 
 def adam_(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, beta1: float = 0.9,
-          beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0):
-    """torch.optim.Adam (non-amsgrad, L2 weight decay) restated on flat fp32 tensors."""
+          beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0,
+          max_grad_norm: Optional[float] = None):
+    """torch.optim.Adam (non-amsgrad, L2 weight decay) restated on flat fp32 tensors.
+    ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_`` on ``grads`` first (the norm from an
+    fp64 sum of squares; a non-finite norm leaves everything untouched)."""
+    if max_grad_norm:
+        norm = float(grads.double().square().sum()) ** 0.5
+        if norm != norm or norm in (float("inf"), float("-inf")):
+            return params
+        coef = torch.tensor(min(1.0, float(max_grad_norm) / (norm + 1e-6)), dtype=torch.float32)
+        grads = grads * coef
     g = grads if weight_decay == 0 else grads + weight_decay * params
     exp_avg.mul_(beta1).add_(g, alpha=1 - beta1)
     exp_avg_sq.mul_(beta2).addcmul_(g, g, value=1 - beta2)

@@ -319,6 +319,11 @@ class FederatedSite:
                 torch.cuda.synchronize()
             dt = time.time() - t0
             itd.append(dt / max(steps, 1))
+            if getattr(trainer.optimizer, "max_grad_norm", None):
+                # clipping on: the last update's gradient norm and the skipped-update count
+                logs.setdefault(f"{tag}grad_norm", []).append(float(trainer.optimizer.grad_norm))
+                logs.setdefault(f"{tag}skipped_steps", []).append(
+                    int(trainer.optimizer.skipped_steps))
             tl.append([round(avg.average, 6)] + met.get((monitor if monitor != "loss" else "auc",)))
             logs.setdefault(f"{tag}samples_per_sec", []).append(nsamp / dt if dt > 0 else 0.0)
             stop = False

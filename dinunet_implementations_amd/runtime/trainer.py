@@ -114,7 +114,9 @@ class NNTrainer:
     def _init_optimizer(self, lr: Optional[float] = None):
         self.flat = FlatParams(self.parameters(), device=self.device["gpu"])
         lr = float(lr if lr is not None else self.cache.get("learning_rate", 1e-3))
-        self.optimizer = FusedAdam(self.flat, lr=lr, weight_decay=float(self.cache.get("weight_decay", 0.0)))
+        # (0 = off -> None, so the DINUNET_MAX_GRAD_NORM switch still applies)
+        self.optimizer = FusedAdam(self.flat, lr=lr, weight_decay=float(self.cache.get("weight_decay", 0.0)),
+                                   max_grad_norm=float(self.cache.get("max_grad_norm") or 0) or None)
 
     def modules(self) -> nn.Module:
         """All registered modules as one container (engines walk ``.modules()``)."""

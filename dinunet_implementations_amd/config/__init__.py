@@ -88,6 +88,13 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     # site loop: train epochs device-fed (runtime.feed: HBM-resident bf16 split, K-step graphs,
     # on-device train records) when the step supports it
     "device_feed": True,
+    # validation / test passes device-fed too (runtime.evalfeed: resident split, captured
+    # forward-only graphs, one host read per pass) when the site can take them; off by default.
+    # Where it is unset, DINUNET_DEVICE_EVAL=1 turns it on
+    "device_eval": False,
+    # rows per validation / test batch (None: batch_size).  A model whose evaluation does not
+    # couple the rows of a batch (ICA) may raise it; refused for batch-statistics BatchNorm (FS)
+    "eval_batch_size": None,
     # classifier / MLP normalisation: "batch" = the reference's BatchNorm1d, "layer" = the
     # optional LayerNorm on its own gfx950 kernels (ops.layernorm)
     "norm_layer": "batch",
@@ -273,6 +280,17 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if isinstance(mg, bool) or not isinstance(mg, (int, float)) or not (0 <= mg <= 3.4e38):
         raise ValueError(f"max_grad_norm must be a number >= 0 (0 = off), got {mg!r}")
     cfg["max_grad_norm"] = mg
+    de = cfg.get("device_eval", False)
+    if de is None:
+        de = False
+    if not isinstance(de, bool):
+        raise ValueError(f"device_eval must be true or false, got {de!r}")
+    cfg["device_eval"] = de
+    eb = cfg.get("eval_batch_size")
+    if eb is not None and (isinstance(eb, bool) or not isinstance(eb, int) or eb < 1):
+        raise ValueError(f"eval_batch_size must be a positive integer (or None: batch_size), "
+                         f"got {eb!r}")
+    cfg["eval_batch_size"] = eb
     cfg["mode"] = str(cfg.get("mode", "train")).lower()
     cfg["metric_direction"] = cfg.get("metric_direction", "maximize")
     return cfg

@@ -194,7 +194,11 @@ template <> struct LdsSplit<192, 16> { static constexpr int FWD_MT = 1, BWD_KS =
 // tile is read once per k-step for 12 MFMAs instead of 4.
 // PT: element type of the stored gate pre-activations (float, or bf16 with
 // DINUNET_LSTM_PRE_BF16: half the bytes the forward writes and the backward reads per step)
-template <int HD, int BR, bool SEQ, int UG, typename PT = float>
+// SAVE: keep what a backward reads (c_save, hprev, pre).  false is the forward-only recurrence
+// (lstm_fwd_infer_kernel: evaluation, no input needs a gradient): none of the three is stored
+// and no descriptor or per-lane offset is built for them; the arithmetic of a step, and so
+// hmean / hseq, hT and cT, is the same to the bit.
+template <int HD, int BR, bool SEQ, int UG, typename PT = float, bool SAVE = true>
 __device__ __forceinline__ void
 fwd_recur(const bf16* xp,                  // [B*S][ndir][4*HD] permuted cols, no bias (bf16)
           const float* __restrict__ bias,  // [ndir][4*HD] permuted + padded, b_ih + b_hh
@@ -288,20 +292,24 @@ fwd_recur(const bf16* xp,                  // [B*S][ndir][4*HD] permuted cols, n
   const int b0 = bx * BR;                         // first batch row of this workgroup (< B)
   const int nrow = B - b0 < BR ? B - b0 : BR;     // its valid rows
   const __amdgpu_buffer_rsrc_t x_rs = dn_rsrc(xp + (long)b0 * S * rowXi, (uint32_t)(nrow * S * rowXi * 2));
+  // (forward-only: the three saved images get empty descriptors that nothing uses)
   const __amdgpu_buffer_rsrc_t pre_rs =
-      dn_rsrc(pre ? pre + (long)b0 * S * rowXi : pre,
-              pre ? (uint32_t)(nrow * S * rowXi * (int)sizeof(PT)) : 0u);
-  const long cb0 = ((long)dir * Bp + b0) * S * HD;  // [ndir][Bp][S][HD] images
-  const __amdgpu_buffer_rsrc_t c_rs = dn_rsrc(c_save + cb0, (uint32_t)(BR * S * HD * 4));
-  const __amdgpu_buffer_rsrc_t hp_rs = dn_rsrc(hprev + cb0, (uint32_t)(BR * S * HD * 2));
-  uint32_t xo[NSL], po[NSL], co[NSL], ho[NSL];  // per-lane byte offsets at time index 0
+      dn_rsrc(SAVE && pre ? pre + (long)b0 * S * rowXi : pre,
+              SAVE && pre ? (uint32_t)(nrow * S * rowXi * (int)sizeof(PT)) : 0u);
+  const long cb0 = SAVE ? ((long)dir * Bp + b0) * S * HD : 0;  // [ndir][Bp][S][HD] images
+  const __amdgpu_buffer_rsrc_t c_rs = dn_rsrc(c_save + cb0, SAVE ? (uint32_t)(BR * S * HD * 4) : 0u);
+  const __amdgpu_buffer_rsrc_t hp_rs = dn_rsrc(hprev + cb0, SAVE ? (uint32_t)(BR * S * HD * 2) : 0u);
+  // per-lane byte offsets at time index 0
+  uint32_t xo[NSL], po[SAVE ? NSL : 1], co[SAVE ? NSL : 1], ho[SAVE ? NSL : 1];
 #pragma unroll
   for (int s = 0; s < NSL; ++s) {
     xo[s] = (uint32_t)(((bc - b0) * S * rowXi + dir * 4 * HD + 4 * uu[s]) * 2);
-    po[s] = b < B ? (uint32_t)(((b - b0) * S * rowXi + dir * 4 * HD + 4 * uu[s]) * (int)sizeof(PT))
-                  : DN_OOB;
-    co[s] = (uint32_t)((((b - b0) * S) * HD + uu[s]) * 4);
-    ho[s] = (uint32_t)((((b - b0) * S) * HD + uu[s]) * 2);
+    if constexpr (SAVE) {
+      po[s] = b < B ? (uint32_t)(((b - b0) * S * rowXi + dir * 4 * HD + 4 * uu[s]) * (int)sizeof(PT))
+                    : DN_OOB;
+      co[s] = (uint32_t)((((b - b0) * S) * HD + uu[s]) * 4);
+      ho[s] = (uint32_t)((((b - b0) * S) * HD + uu[s]) * 2);
+    }
   }
   const uint32_t xstep = (uint32_t)(rowXi * 2);  // bytes per time index (bf16 projection)
   const uint32_t pstep = (uint32_t)(rowXi * (int)sizeof(PT));  // (pre-activations)
@@ -312,7 +320,7 @@ fwd_recur(const bf16* xp,                  // [B*S][ndir][4*HD] permuted cols, n
   };
   // h_{t-1} for the weight-gradient GEMMs: each lane stores the h it produces into step t+1's
   // slot (the last step's h has no slot: out-of-range offset, dropped); slot 0 holds h_{-1} = 0
-  {
+  if constexpr (SAVE) {
     const int tau0 = dir == 0 ? 0 : S - 1;
 #pragma unroll
     for (int s = 0; s < NSL; ++s)
@@ -447,7 +455,9 @@ fwd_recur(const bf16* xp,                  // [B*S][ndir][4*HD] permuted cols, n
       const float p3 = pa[s][3] + (float)xn[s][3] + bb[3];
       // the gate pre-activations x W_ih^T + h W_hh^T + b, in place of the projection they were
       // built from: the backward reads them instead of re-running a time-parallel GEMM
-      if constexpr (sizeof(PT) == 4) {
+      if constexpr (!SAVE) {
+        // forward-only: nothing reads the pre-activations
+      } else if constexpr (sizeof(PT) == 4) {
         dn_store_f32x4(pre_rs, po[s] + (uint32_t)tau * pstep, f32x4{p0, p1, p2, p3});
       } else {
         const bf16x4 pe = bf16x4{(bf16)p0, (bf16)p1, (bf16)p2, (bf16)p3};
@@ -459,18 +469,28 @@ fwd_recur(const bf16* xp,                  // [B*S][ndir][4*HD] permuted cols, n
       const float gf = sigmoid_unit(dn_sigmoid(p1));
       const float go = sigmoid_unit(dn_sigmoid(p2));
       const float gg = dn_tanh(p3);
-      c[s] = gf * c[s] + gi * gg;
+      if constexpr (SAVE || EARLY) {
+        c[s] = gf * c[s] + gi * gg;
+      } else {
+        // forward-only, late-prefetch geometries (4 gate slots per lane, or 2 at 512 units): left
+        // to -ffp-contract, hipcc fuses gf * c into the fma here but gi * gg in the storing
+        // kernel, and the cell states differ in the last bit.  Written out as the storing
+        // kernel's form (tests/test_lstm_infer_gpu.py compares every instantiation bitwise).
+        c[s] = __builtin_fmaf(gi, gg, gf * c[s]);
+      }
       const float h = go * dn_tanh(c[s]);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[s]), c_rs,
-                                            (int)(co[s] + (uint32_t)(tau * HD * 4)), 0, 0);
+      if constexpr (SAVE)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, c[s]), c_rs,
+                                              (int)(co[s] + (uint32_t)(tau * HD * 4)), 0, 0);
       if constexpr (SEQ) hseq[((long)b * S + t) * ndir * HD + dir * HD + u] = h;
       hs[s] += h;
       hl[s] = h;
       const bf16 hb16 = (bf16)h;
       hbuf[nxt][bl][u] = hb16;
-      __builtin_amdgcn_raw_buffer_store_b16(
-          __builtin_bit_cast(unsigned short, hb16), hp_rs,
-          (int)(t + 1 < S ? ho[s] + (uint32_t)(tau1 * HD * 2) : DN_OOB), 0, 0);
+      if constexpr (SAVE)
+        __builtin_amdgcn_raw_buffer_store_b16(
+            __builtin_bit_cast(unsigned short, hb16), hp_rs,
+            (int)(t + 1 < S ? ho[s] + (uint32_t)(tau1 * HD * 2) : DN_OOB), 0, 0);
     }
 #ifdef DN_STAMPS
     STAMP(ts2);
@@ -522,6 +542,18 @@ lstm_fwd_kernel(const bf16* xp, const float* __restrict__ bias, const bf16* __re
   fwd_recur<HD, BR, SEQ, UG, PT>(xp, bias, whh, B, S, Hd, ndir, c_save, hprev, hseq, hmean,
                                  mean_scale, hT, cT, pre, bsplit, (int)blockIdx.x,
                                  (int)blockIdx.y, (int)gridDim.x);
+}
+
+// forward-only recurrence (fwd_recur SAVE = false): no c_save / hprev / pre arguments at all
+template <int HD, int BR, bool SEQ, int UG>
+__global__ void __launch_bounds__(HD / (16 * UG) * 64)
+lstm_fwd_infer_kernel(const bf16* xp, const float* __restrict__ bias,
+                      const bf16* __restrict__ whh, int B, int S, int Hd, int ndir,
+                      float* __restrict__ hseq, float* __restrict__ hmean, float mean_scale,
+                      float* __restrict__ hT, float* __restrict__ cT, int bsplit) {
+  fwd_recur<HD, BR, SEQ, UG, float, false>(xp, bias, whh, B, S, Hd, ndir, nullptr, nullptr, hseq,
+                                           hmean, mean_scale, hT, cT, nullptr, bsplit,
+                                           (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1025,6 +1057,51 @@ int launch_fwd(int BR, const bf16* xp, const float* bias, const bf16* whh, int B
   }
 }
 
+// forward-only launchers: the same (BR, UG) choice per geometry as the storing forward
+template <int HD, int BR, int UG>
+int launch_infer_ug(const bf16* xp, const float* bias, const bf16* whh, int B, int S, int Hd,
+                    int ndir, float* hseq, float* hmean, float mean_scale, float* hT, float* cT,
+                    int bsplit, hipStream_t st) {
+  dim3 grid((B + BR - 1) / BR, ndir), block(HD / (16 * UG) * 64);
+  if (hseq)
+    hipLaunchKernelGGL((lstm_fwd_infer_kernel<HD, BR, true, UG>), grid, block, 0, st, xp, bias,
+                       whh, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bsplit);
+  else
+    hipLaunchKernelGGL((lstm_fwd_infer_kernel<HD, BR, false, UG>), grid, block, 0, st, xp, bias,
+                       whh, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bsplit);
+  return dn_launch_status();
+}
+
+template <int HD, int BR>
+int launch_infer_br(const bf16* xp, const float* bias, const bf16* whh, int B, int S, int Hd,
+                    int ndir, float* hseq, float* hmean, float mean_scale, float* hT, float* cT,
+                    int bsplit, hipStream_t st) {
+  if constexpr (HD == 192 && BR == 4) {
+    if (lstm_ug() == 3)
+      return launch_infer_ug<HD, BR, 3>(xp, bias, whh, B, S, Hd, ndir, hseq, hmean, mean_scale,
+                                        hT, cT, bsplit, st);
+  }
+  return launch_infer_ug<HD, BR, (HD > 256 ? 2 : 1)>(xp, bias, whh, B, S, Hd, ndir, hseq, hmean,
+                                                     mean_scale, hT, cT, bsplit, st);
+}
+
+template <int HD>
+int launch_infer(int BR, const bf16* xp, const float* bias, const bf16* whh, int B, int S, int Hd,
+                 int ndir, float* hseq, float* hmean, float mean_scale, float* hT, float* cT,
+                 int bsplit, hipStream_t st) {
+  if (BR == 4)
+    return launch_infer_br<HD, 4>(xp, bias, whh, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT,
+                                  bsplit, st);
+  if constexpr (HD > 192) return DN_UNSUPPORTED;  // streamed variants: 4 rows only (pick_br)
+  else {
+    if (BR == 8)
+      return launch_infer_br<HD, 8>(xp, bias, whh, B, S, Hd, ndir, hseq, hmean, mean_scale, hT,
+                                    cT, bsplit, st);
+    return launch_infer_br<HD, 16>(xp, bias, whh, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT,
+                                   bsplit, st);
+  }
+}
+
 template <int HD, int BR, int UG>
 int launch_bwd_ug(const float* pre, const float* c_save, const bf16* whhT, const float* dh_ext,
                   long sb, long st_, float scale, const float* dhT, const float* dcT, int B, int S,
@@ -1223,6 +1300,32 @@ DN_API int dn_lstm_fwd(const void* xp, const float* bias, const void* whh_p, int
     case 256: return launch_fwd<256>(BR, (const bf16*)xp, bias, (const bf16*)whh_p, B, S, Hd, ndir, c_save, (bf16*)hprev, hseq, hmean, mean_scale, hT, cT, pre, pre_bf16, st);
     case 384: return launch_fwd<384>(BR, (const bf16*)xp, bias, (const bf16*)whh_p, B, S, Hd, ndir, c_save, (bf16*)hprev, hseq, hmean, mean_scale, hT, cT, pre, pre_bf16, st);
     case 512: return launch_fwd<512>(BR, (const bf16*)xp, bias, (const bf16*)whh_p, B, S, Hd, ndir, c_save, (bf16*)hprev, hseq, hmean, mean_scale, hT, cT, pre, pre_bf16, st);
+  }
+  return DN_UNSUPPORTED;
+}
+
+// dn_lstm_fwd without a backward to follow (evaluation): the same recurrence, rows per workgroup
+// and outputs -- hmean, or hseq [Bp][S][ndir*HD] with Bp = B padded to dn_lstm_rows_per_wg, and
+// hT / cT (bitwise those of dn_lstm_fwd) -- but nothing is kept for a backward, so the caller
+// allocates no c_save, hprev or pre.
+DN_API int dn_lstm_fwd_infer(const void* xp, const float* bias, const void* whh_p, int B, int S,
+                             int Hd, int ndir, float* hseq, float* hmean, float mean_scale,
+                             float* hT, float* cT, int bias_split, hipStream_t st) {
+  const int HD = dn_lstm_padded_hidden(Hd);
+  if (!HD || B <= 0 || S <= 0 || ndir < 1 || ndir > 2) return DN_BAD_SHAPE;
+  if (bias_split != 0 && bias_split != ndir * 4 * HD) return DN_BAD_SHAPE;
+  if (!xp || !bias || !whh_p || (!hseq && !hmean)) return DN_BAD_SHAPE;
+  const int BR = pick_br(B, HD);
+  if (!lstm_fits_32bit(B, S, HD, ndir, BR)) return DN_BAD_SHAPE;
+  const bf16* x = (const bf16*)xp;
+  const bf16* w = (const bf16*)whh_p;
+  switch (HD) {
+    case 64: return launch_infer<64>(BR, x, bias, w, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bias_split, st);
+    case 128: return launch_infer<128>(BR, x, bias, w, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bias_split, st);
+    case 192: return launch_infer<192>(BR, x, bias, w, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bias_split, st);
+    case 256: return launch_infer<256>(BR, x, bias, w, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bias_split, st);
+    case 384: return launch_infer<384>(BR, x, bias, w, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bias_split, st);
+    case 512: return launch_infer<512>(BR, x, bias, w, B, S, Hd, ndir, hseq, hmean, mean_scale, hT, cT, bias_split, st);
   }
   return DN_UNSUPPORTED;
 }

@@ -9,7 +9,9 @@ forward
   3. ``dn_lstm_fwd``: persistent recurrence (grid = batch-row chunks x directions), stores
      ``c_t`` and ``h_{t-1}`` per step and, when a backward will follow, the gate
      pre-activations ``x W_ih^T + h_{t-1} W_hh^T + b`` (fp32, one 16-B store per lane and
-     step, no extra GEMM).
+     step, no extra GEMM).  When no input needs a gradient (evaluation under ``no_grad``):
+     ``dn_lstm_fwd_infer``, the same recurrence storing none of the three -- they are not even
+     allocated -- with outputs bitwise those of ``dn_lstm_fwd``.
 backward
   4. (nothing to recompute: the forward stored the pre-activations).
   5. ``dn_lstm_bwd``: reverse-time recurrence -> gate grads ``dpre`` (bf16, original time order).
@@ -53,6 +55,10 @@ _lib.register("dn_lstm_fwd", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.
                               _lib.c_int, _lib.c_int, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
                               _lib.c_void_p, _lib.c_float, _lib.c_void_p, _lib.c_void_p,
                               _lib.c_void_p, _lib.c_int, _lib.c_int, _lib.c_void_p])
+_lib.register("dn_lstm_fwd_infer", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_int,
+                                    _lib.c_int, _lib.c_int, _lib.c_int, _lib.c_void_p,
+                                    _lib.c_void_p, _lib.c_float, _lib.c_void_p, _lib.c_void_p,
+                                    _lib.c_int, _lib.c_void_p])
 _lib.register("dn_lstm_bwd", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
                               _lib.c_long, _lib.c_long, _lib.c_float, _lib.c_void_p,
                               _lib.c_void_p, _lib.c_int, _lib.c_int, _lib.c_int, _lib.c_int,
@@ -124,7 +130,7 @@ def _ones(n: int, device) -> Tensor:
 class _BiLSTMFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, enc: Tensor, mode: str, modules, packed, xp_pre, relu_in: bool,
-                *params: Tensor):
+                grad_on: bool, *params: Tensor):
         ctx.set_materialize_grads(False)  # unused hT / cT -> None (no zero tensors, no syncs)
         B, S, I = enc.shape
         ndir = len(params) // 4
@@ -152,8 +158,9 @@ class _BiLSTMFn(torch.autograd.Function):
             # bf16 projection: half the bytes the recurrence streams per step (large batches
             # are HBM-bound there); the sum with the recurrent part stays fp32
             xp = mm_plain(x2d, wih_p, trans_b=True, out_dtype=torch.bfloat16)  # [B*S, ndir*GP]
-        c_save = torch.empty(ndir, Bp, S, HD, dtype=torch.float32, device=dev)
-        hprev = torch.empty(ndir, Bp, S, HD, dtype=torch.bfloat16, device=dev)
+        # (grad_on: the caller's grad mode -- it is always off in here, and needs_input_grad
+        # only says which inputs require a gradient)
+        need_bwd = bool(grad_on) and any(ctx.needs_input_grad)
         hT = torch.empty(B, ndir * Hd, dtype=torch.float32, device=dev)
         cT = torch.empty(B, ndir * Hd, dtype=torch.float32, device=dev)
         hmean = hseq = None
@@ -161,21 +168,29 @@ class _BiLSTMFn(torch.autograd.Function):
             hmean = torch.empty(B, ndir * Hd, dtype=torch.float32, device=dev)
         else:
             hseq = torch.empty(Bp, S, ndir * HD, dtype=torch.float32, device=dev)
-        need_bwd = any(ctx.needs_input_grad)
-        # gate pre-activations (x W_ih^T + h W_hh^T + b) for the backward (fp32, or bf16: pre_dtype)
-        pre = (torch.empty(B * S, ndir * GP, dtype=pre_dtype(B, Hd, mode), device=dev)
-               if need_bwd else None)
         # a persistent pack (PersistentPack) keeps b_ih and b_hh as two images: summed in-kernel
         bsplit = ndir * GP if bias_p.numel() == 2 * ndir * GP else 0
-        _lib.call("dn_lstm_fwd", xp.data_ptr(), bias_p.data_ptr(), whh_p.data_ptr(), B, S, Hd,
-                  ndir, c_save.data_ptr(), hprev.data_ptr(), _lib.ptr(hseq), _lib.ptr(hmean),
-                  1.0 / S, hT.data_ptr(), cT.data_ptr(), _lib.ptr(pre), bsplit,
-                  int(pre is not None and pre.dtype == torch.bfloat16), st)
+        if need_bwd:
+            c_save = torch.empty(ndir, Bp, S, HD, dtype=torch.float32, device=dev)
+            hprev = torch.empty(ndir, Bp, S, HD, dtype=torch.bfloat16, device=dev)
+            # gate pre-activations (x W_ih^T + h W_hh^T + b) for the backward (fp32, or bf16:
+            # pre_dtype)
+            pre = torch.empty(B * S, ndir * GP, dtype=pre_dtype(B, Hd, mode), device=dev)
+            _lib.call("dn_lstm_fwd", xp.data_ptr(), bias_p.data_ptr(), whh_p.data_ptr(), B, S, Hd,
+                      ndir, c_save.data_ptr(), hprev.data_ptr(), _lib.ptr(hseq), _lib.ptr(hmean),
+                      1.0 / S, hT.data_ptr(), cT.data_ptr(), pre.data_ptr(), bsplit,
+                      int(pre.dtype == torch.bfloat16), st)
+            ctx.save_for_backward(x2d, wih_p, whh_p, whhT_p, bias_p, pre, c_save, hprev)
+        else:
+            # no input needs a gradient (evaluation): the forward-only recurrence, which stores
+            # none of c_save / hprev / pre -- the same outputs to the bit
+            _lib.call("dn_lstm_fwd_infer", xp.data_ptr(), bias_p.data_ptr(), whh_p.data_ptr(), B,
+                      S, Hd, ndir, _lib.ptr(hseq), _lib.ptr(hmean), 1.0 / S, hT.data_ptr(),
+                      cT.data_ptr(), bsplit, st)
         if mode == "mean":
             out = hmean
         else:
             out = hseq.view(Bp, S, ndir, HD)[:B, :, :, :Hd].reshape(B, S, ndir * Hd)
-        ctx.save_for_backward(x2d, wih_p, whh_p, whhT_p, bias_p, pre, c_save, hprev)
         ctx.params = params
         ctx.relu_in = bool(relu_in)
         ctx.meta = (B, S, I, Hd, HD, ndir, mode, enc.dtype)
@@ -189,7 +204,7 @@ class _BiLSTMFn(torch.autograd.Function):
         # a differentiable precomputed projection (``project``: split capture at the projection
         # output) receives the gate gradients themselves: d xp = dpre
         dxp = dpre_v if ctx.needs_input_grad[4] else None
-        return (dx, None, None, None, dxp, None) + (None,) * len(ctx.params)
+        return (dx, None, None, None, dxp, None, None) + (None,) * len(ctx.params)
 
 
 def _lstm_backward(ctx, saved, dout: Optional[Tensor], dhT: Optional[Tensor],
@@ -553,5 +568,5 @@ def bilstm(x: Tensor, params: Sequence[Tuple[Tensor, Tensor, Tensor, Tensor]],
     for p in params:
         flat.extend(p)
     out, hT, cT = _BiLSTMFn.apply(x, "mean" if reduce == "mean" else "seq", modules, packed, xp,
-                                  bool(relu_input), *flat)
+                                  bool(relu_input), torch.is_grad_enabled(), *flat)
     return out, (hT, cT)

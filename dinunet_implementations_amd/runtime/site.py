@@ -39,6 +39,7 @@ from ..utils import logs as L
 from ..utils.metrics import Averages, Metrics, improved, metric_value
 from ..ops import FusedAdam
 from . import health
+from .evalfeed import EvalFeed, resident_bytes
 from .feed import DeviceFeed
 from .step import TrainStep
 from .trainer import NNTrainer, set_seed
@@ -112,6 +113,22 @@ class _PretrainSignal:
         return False
 
 
+def check_eval_batch_size(cfg: Dict[str, Any], trainer: NNTrainer) -> None:
+    """``eval_batch_size`` other than ``batch_size`` changes the scores of a model whose
+    evaluation couples the rows of a batch: a BatchNorm that normalises with batch statistics in
+    evaluation too (the FS model, ``track_running_stats=False``).  Refused for such a model."""
+    ebs = cfg.get("eval_batch_size")
+    if ebs is None or int(ebs) == int(cfg.get("batch_size", 16)):
+        return
+    for net in trainer.nn.values():
+        for m in net.modules():
+            if isinstance(m, torch.nn.modules.batchnorm._BatchNorm) and not m.track_running_stats:
+                raise ValueError(
+                    f"eval_batch_size {ebs} != batch_size {cfg.get('batch_size', 16)}: this model's "
+                    "BatchNorm normalises with batch statistics in evaluation too, so its "
+                    "validation and test scores depend on the batch size")
+
+
 class FederatedSite:
     def __init__(self, cfg: Dict[str, Any], group: SiteGroup, trainer_cls, dataset_cls,
                  datahandle_cls, state: Dict[str, Any], out_dir: str, site_name: Optional[str] = None,
@@ -125,6 +142,8 @@ class FederatedSite:
         self.device = group.device
         self.verbose = verbose
         self.task_id = str(cfg.get("task_id"))
+        self._eval_feeds: Dict[Any, Optional[EvalFeed]] = {}  # per (trainer, split) of a fold
+        self._eval_off_logged = False
 
     # ---------------------------------------------------------------------------------------
     def log(self, *a):
@@ -153,13 +172,16 @@ class FederatedSite:
             out[key] = (X, y)
         return out
 
-    def _batch_size(self, cfg: Dict[str, Any]) -> int:
-        """Rows per step on this process: the site's ``batch_size`` split over its replicas."""
-        bs = int(cfg.get("batch_size", 16))
+    def _batch_size(self, cfg: Dict[str, Any], key: str = "batch_size") -> int:
+        """Rows per step on this process: the site's ``batch_size`` split over its replicas
+        (``key="eval_batch_size"``: rows per validation / test batch, ``batch_size`` when unset)."""
+        if cfg.get(key) is None:
+            key = "batch_size"
+        bs = int(cfg.get(key, 16))
         k = self.group.replicas
         if k > 1:
             if bs % k:
-                raise ValueError(f"batch_size {bs} does not split over the site's {k} GPUs")
+                raise ValueError(f"{key} {bs} does not split over the site's {k} GPUs")
             bs //= k
         return bs
 
@@ -171,9 +193,60 @@ class FederatedSite:
             drop_last = False  # keep at least one batch on tiny splits
         return DeviceLoader(X, y, batch_size, shuffle=shuffle, drop_last=drop_last, seed=seed)
 
-    # ---- global evaluation ------------------------------------------------------------------
-    def global_eval(self, trainer: NNTrainer, loader: DeviceLoader):
-        res = trainer.evaluate(loader)
+    # ---- evaluation -------------------------------------------------------------------------
+    def _device_eval_off(self, why: str) -> None:
+        if not self._eval_off_logged:
+            self._eval_off_logged = True
+            self.log(f"device_eval off, evaluating from the host loop: {why}")
+        return None
+
+    def _eval_feed(self, trainer: NNTrainer, loader: DeviceLoader, cfg: Dict[str, Any],
+                   logs: Optional[Dict[str, Any]]) -> Optional[EvalFeed]:
+        """The device-fed pass (``runtime.evalfeed``) over ``loader``'s split when ``device_eval``
+        (or ``DINUNET_DEVICE_EVAL=1`` where the key is unset) asks for it and this site can take
+        it: a GPU, the fused compute path, a plugin with ``forward_loss`` and a score column, and
+        room in HBM for the feed's copy of the split.  One feed per trainer and split, kept for
+        the fold.  Otherwise None (the host loop), the reason logged once."""
+        if not (cfg.get("device_eval") or os.environ.get("DINUNET_DEVICE_EVAL", "") == "1"):
+            return None
+        key = (id(trainer), id(loader.inputs), loader.batch_size)
+        if key in self._eval_feeds:
+            return self._eval_feeds[key]
+        X = loader.inputs
+        feed = None
+        if self.device.type != "cuda" or not X.is_cuda:
+            self._device_eval_off("not on a GPU")
+        elif trainer.reference_math:
+            self._device_eval_off('compute_path is not "fused"')
+        elif not trainer.has_fast_path or getattr(trainer, "score_column", None) is None:
+            self._device_eval_off("the trainer has no forward_loss / score_column")
+        elif X.shape[0] < 1:
+            pass  # an empty split: nothing to feed
+        else:
+            sm = trainer.split_module()
+            need = resident_bytes(X, bool(getattr(sm, "accepts_bf16_input", False)))
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if need > 0.9 * free:
+                self._device_eval_off(f"its copy of the split ({need / 2**30:.2f} GiB) does not "
+                                      f"fit the free HBM ({free / 2**30:.2f} GiB)")
+            else:
+                try:
+                    feed = EvalFeed(trainer, X, loader.labels, loader.batch_size, group=self.group)
+                except ValueError as e:  # a sample layout the resident gather does not take
+                    self._device_eval_off(str(e))
+        self._eval_feeds[key] = feed
+        if feed is not None and logs is not None:
+            logs["eval_feed"] = "device"
+        return feed
+
+    def _evaluate(self, trainer: NNTrainer, loader: DeviceLoader, cfg: Optional[Dict[str, Any]] = None,
+                  logs: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        feed = self._eval_feed(trainer, loader, cfg if cfg is not None else self.cfg, logs)
+        return feed.run() if feed is not None else trainer.evaluate(loader)
+
+    def global_eval(self, trainer: NNTrainer, loader: DeviceLoader,
+                    cfg: Optional[Dict[str, Any]] = None, logs: Optional[Dict[str, Any]] = None):
+        res = self._evaluate(trainer, loader, cfg, logs)
         avg: Averages = res["averages"]
         met: Metrics = res["metrics"]
         s, l = met.tensors()
@@ -211,7 +284,8 @@ class FederatedSite:
         bs = self._batch_size(cfg)
         li = max(1, int(cfg.get("local_iterations", 1)))
         tr = self._loader(*data["train"], "train", bs, seed)
-        va = self._loader(*data["validation"], "validation", bs, seed)
+        va = self._loader(*data["validation"], "validation",
+                          self._batch_size(cfg, "eval_batch_size"), seed)
         local_steps = max(1, math.ceil(len(tr) / li)) if tr.num_samples else 0
         if group is self.group:
             steps = self._global_max(local_steps)
@@ -329,9 +403,9 @@ class FederatedSite:
             stop = False
             if epoch % val_every == 0:
                 if group is self.group:
-                    r = self.global_eval(trainer, va)
+                    r = self.global_eval(trainer, va, cfg, logs)
                 else:
-                    res = trainer.evaluate(va)
+                    res = self._evaluate(trainer, va, cfg, logs)
                     r = {"loss": res["averages"].average, "scores": res["metrics"].scores(),
                          "local_loss": res["averages"].average, "local_scores": res["metrics"].scores()}
                 score = r["loss"] if monitor.lower() == "loss" else metric_value(r["scores"], monitor)
@@ -502,6 +576,8 @@ class FederatedSite:
         }
         trainer = self.Trainer(cache=cfg, state=self.state, device=self.device)
         trainer.init_nn(seed=int(cfg.get("seed", 0) or 0) + fold)  # same init on every site
+        check_eval_batch_size(cfg, trainer)
+        self._eval_feeds = {}  # (feeds hold the previous fold's trainer and splits)
         self._broadcast_model(trainer, 0)
         start_epoch, best, resume = 1, None, None
         last = os.path.join(fdir, "checkpoint_last.pt")
@@ -538,8 +614,8 @@ class FederatedSite:
             if hasattr(engine, "close"):
                 engine.close()
             trainer.load_checkpoint(os.path.join(fdir, "checkpoint_best.pt"))
-        te = self._loader(*data["test"], "test", self._batch_size(cfg), seed)
-        r = self.global_eval(trainer, te)
+        te = self._loader(*data["test"], "test", self._batch_size(cfg, "eval_batch_size"), seed)
+        r = self.global_eval(trainer, te, cfg, logs)
         logs["test_metrics"] = L.test_row(r["loss"], r["scores"])
         logs["local_test_metrics"] = L.test_row(r["local_loss"], r["local_scores"])
         logs["test_scores"] = r["scores"]

@@ -64,6 +64,12 @@ class LocalNode:
     def _setup(self, inp: Dict[str, Any], state: Dict[str, Any]):
         self.state = state
         self.cfg = build_config(site_input=inp, **self.code_defaults)
+        if self.cfg.get("class_weights") == "balanced":
+            # the phase machines exchange no label counts: the in-process runtime
+            # (runtime.site.FederatedSite) computes "balanced"; here the list must be given
+            raise ValueError("class_weights='balanced' is computed by the in-process runtime "
+                             "(runtime.site) from every site's label counts; the COINSTAC phase "
+                             "machines need the explicit list of class weights")
         if not self._device_arg:
             from ..parallel.group import resolve_device
             self.device = resolve_device(self.cfg.get("gpus"))

@@ -76,6 +76,14 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     "dsgd_bucket_mb": 4.0,
     # global-norm gradient clipping in the fused Adam (ops.FusedAdam max_grad_norm): 0 = off
     "max_grad_norm": 0,
+    # loss options of the fused classifier heads (ops.head): F.cross_entropy's per-class weight
+    # and label smoothing, every batch normalised by its own sum_i weight[y_i].  class_weights:
+    # None, a list of num_class finite numbers > 0, or "balanced" (n_total / (C * n_c) from the
+    # label counts of every site's training split, runtime.site).  Where they are unset (None /
+    # 0), DINUNET_CLASS_WEIGHTS (a comma list) / DINUNET_LABEL_SMOOTHING (a number) apply
+    # (ops.HeadSpec)
+    "class_weights": None,
+    "label_smoothing": 0,
     "rccl_algo": None,
     "rccl_proto": None,
     "collective_timeout_s": 1800,
@@ -280,6 +288,24 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if isinstance(mg, bool) or not isinstance(mg, (int, float)) or not (0 <= mg <= 3.4e38):
         raise ValueError(f"max_grad_norm must be a number >= 0 (0 = off), got {mg!r}")
     cfg["max_grad_norm"] = mg
+    ls = cfg.get("label_smoothing", 0)
+    ls = 0 if ls is None else ls
+    if isinstance(ls, bool) or not isinstance(ls, (int, float)) or not (0 <= ls < 1):
+        raise ValueError(f"label_smoothing must be a number in [0, 1), got {ls!r}")
+    cfg["label_smoothing"] = ls
+    cw = cfg.get("class_weights")
+    if isinstance(cw, str):
+        if cw != "balanced":
+            raise ValueError(f"class_weights must be a list of num_class numbers > 0, "
+                             f"'balanced' or None, got {cw!r}")
+    elif cw is not None:
+        nc = int(cfg.get("num_class", 2))
+        if (not isinstance(cw, (list, tuple)) or len(cw) != nc
+                or any(isinstance(v, bool) or not isinstance(v, (int, float)) or v != v
+                       or v in (float("inf"), float("-inf")) or v <= 0 for v in cw)):
+            raise ValueError(f"class_weights must be a list of {nc} finite numbers > 0, "
+                             f"'balanced' or None, got {cw!r}")
+        cfg["class_weights"] = [float(v) for v in cw]
     de = cfg.get("device_eval", False)
     if de is None:
         de = False

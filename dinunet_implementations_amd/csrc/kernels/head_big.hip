@@ -34,6 +34,7 @@
 // the bias gradient partials are sums of the real dZ_l).
 // The last layer must be a plain Linear (no BatchNorm / ReLU after the logits), as in both heads.
 #include "head_common.h"
+#include "loss_opt.h"
 
 namespace {
 
@@ -84,8 +85,8 @@ struct BLayer {
 struct BArgs {
   BLayer L[BMAXL];
   int nl, B, nrb, train, log_out;
-  long g_off;   // fp32 [B][C] p - onehot
-  long gs_off;  // fp32 [16] its column sums
+  long g_off;   // fp32 [B][C] p - onehot (loss options: the weighted, smoothed form), unscaled
+  long gs_off;  // fp32 [17] its column sums, then (loss options) the denominator sum_i w[y_i]
 };
 
 // gW of layer l += its RS row-split partials, added in split order (deterministic); workgroup
@@ -444,11 +445,15 @@ headb_ln_bwd_kernel(BArgs a, int l, char* __restrict__ ws, RedJob rj) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// LW: the loss options are on (lossp: the block of loss_opt.h); LW = false is the plain mean
+// cross-entropy, unchanged.
+template <bool LW>
 __global__ void __launch_bounds__(LOSS_NT)
 headb_loss_kernel(BArgs a, const long long* __restrict__ y, float* __restrict__ out,
                   float* __restrict__ loss, long long* __restrict__ pred,
-                  unsigned long long* __restrict__ rng, char* __restrict__ ws) {
-  __shared__ float red[LOSS_NT / 64][17];
+                  unsigned long long* __restrict__ rng, char* __restrict__ ws,
+                  const float* __restrict__ lossp) {
+  __shared__ float red[LOSS_NT / 64][18];
   const BLayer& L = a.L[a.nl - 1];
   const int C = L.out, B = a.B;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -469,6 +474,11 @@ headb_loss_kernel(BArgs a, const long long* __restrict__ y, float* __restrict__ 
   float gs[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) gs[c] = 0.f;
+  // loss options: the unscaled weighted / smoothed d logits go to g and gs, and D = sum_i w[y_i]
+  // (rows over threads, wave butterfly, waves in order) to gs[16] for the backward's scale
+  LossOpt lo{1.f, 0.f, 0.f};
+  if constexpr (LW) lo = lo_load(lossp);
+  float dsum = 0.f;
   for (int m = tid; m < B; m += LOSS_NT) {
     float v[16];
 #pragma unroll
@@ -488,22 +498,39 @@ headb_loss_kernel(BArgs a, const long long* __restrict__ y, float* __restrict__ 
     long long yc = y[m];
     yc = yc < 0 ? 0 : (yc >= C ? C - 1 : yc);
     float vy = 0.f;
+    float wy = 0.f;
+    if constexpr (LW) wy = lossp[DN_LOSS_W0 + yc];
+    const float awy = lo_mul(lo.a, wy), coef = awy + lo.eW;
+    float S = 0.f;
+    dsum += wy;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       if (c >= C) continue;
       const float lp = v[c] - lse;
       const float p = expf(lp);
       out[(long)m * C + c] = a.log_out ? lp : p;
-      const float gv = p - (c == yc ? 1.f : 0.f);
+      float gv;
+      if constexpr (LW) {
+        const float wc = lossp[DN_LOSS_W0 + c];
+        gv = lo_grad(p, c == yc, awy, coef, lo_mul(lo.e, wc));
+        S += lo_mul(wc, lse - v[c]);
+      } else {
+        gv = p - (c == yc ? 1.f : 0.f);
+      }
       if (train) g[(long)m * C + c] = gv;
       gs[c] += gv;
       vy = c == yc ? v[c] : vy;
     }
-    ls += lse - vy;
+    if constexpr (LW) ls += lo_row(lo, awy, lse - vy, S);
+    else ls += lse - vy;
     pred[m] = am;
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) ls += __shfl_xor(ls, off);
+  if constexpr (LW) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) dsum += __shfl_xor(dsum, off);
+  }
   // (only the C real classes: a wave-wide sum is 6 cross-lane steps, 96 for all 16 slots)
 #pragma unroll
   for (int c = 0; c < 16; ++c)
@@ -513,6 +540,7 @@ headb_loss_kernel(BArgs a, const long long* __restrict__ y, float* __restrict__ 
     }
   if (lane == 0) {
     red[wid][16] = ls;
+    if constexpr (LW) red[wid][17] = dsum;
 #pragma unroll
     for (int c = 0; c < 16; ++c) red[wid][c] = c < C ? gs[c] : 0.f;
   }
@@ -521,7 +549,13 @@ headb_loss_kernel(BArgs a, const long long* __restrict__ y, float* __restrict__ 
     float t = 0.f;
     for (int w = 0; w < LOSS_NT / 64; ++w) t += red[w][tid];
     if (tid == 16) {
-      *loss = t / (float)B;
+      float D = (float)B;
+      if constexpr (LW) {
+        D = 0.f;
+        for (int w = 0; w < LOSS_NT / 64; ++w) D += red[w][17];
+        if (train) reinterpret_cast<float*>(ws + a.gs_off)[16] = D;
+      }
+      *loss = t / D;
     } else if (train) {
       reinterpret_cast<float*>(ws + a.gs_off)[tid] = t;
     }
@@ -618,10 +652,12 @@ headb_bn_bwd_kernel(BArgs a, int l, char* __restrict__ ws, RedJob rj) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// lw (last layer): the loss options were on in the forward, whose loss launch left the
+// denominator sum_i w[y_i] next to the column sums
 template <bool LAST, bool VW>
 __global__ void __launch_bounds__(BNT)
 headb_bwd_kernel(BArgs a, int l, char* __restrict__ ws, const float* __restrict__ dloss,
-                 float* __restrict__ dx, long lddx, int nA, int RS, RedJob rj) {
+                 float* __restrict__ dx, long lddx, int nA, int RS, RedJob rj, int lw) {
   if (rj.rl >= 0 && (int)blockIdx.x >= rj.r0) {
     dw_reduce_body(a, rj.rl, ws, rj.rs, blockIdx.x - rj.r0, gridDim.x - rj.r0);
     return;
@@ -632,7 +668,11 @@ headb_bwd_kernel(BArgs a, int l, char* __restrict__ ws, const float* __restrict_
   const int K = L.in, N = L.out, B = a.B;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nkb = (K + TB - 1) / TB;
-  const float gscale = LAST ? *dloss / (float)B : 1.f;
+  float gscale = 1.f;
+  if (LAST) {
+    if (lw) gscale = *dloss / reinterpret_cast<const float*>(ws + a.gs_off)[16];
+    else gscale = *dloss / (float)B;
+  }
   const float* g = reinterpret_cast<const float*>(ws + a.g_off);
   bf16* dz = reinterpret_cast<bf16*>(ws + L.dz_off);
   const int sr = tid >> 4, sq = (tid & 15) * 4;
@@ -931,7 +971,7 @@ static bool bplan(int nl, const int* dims, const int* flags, const float* drops,
   a.g_off = off;
   off = al256(off + 4L * B * dims[nl]);
   a.gs_off = off;
-  off = al256(off + 4L * 16);
+  off = al256(off + 4L * 17);
   for (int l = 0; l < nl; ++l) {
     BLayer& L = a.L[l];
     const int nkb = (L.in + TB - 1) / TB, nW = ((L.out + TB - 1) / TB) * nkb;
@@ -970,11 +1010,12 @@ int headb_layout(int nl, const int* dims, const int* flags, int B, long* out) {
 int headb_fwd(int nl, const int* dims, const int* flags, const float* drops, const float* bnp,
               void* const* ptrs, const float* x, long ldx, int B, const long long* y, float* out,
               float* loss, long long* pred, unsigned long long* rng, void* ws, int train,
-              int log_out, hipStream_t st) {
+              int log_out, const float* lossp, hipStream_t st) {
   BPlan p;
   if (!bplan(nl, dims, flags, drops, bnp, ptrs, B, p)) return DN_UNSUPPORTED;
   p.a.train = train;
   p.a.log_out = log_out;
+
   for (int l = 0; l < nl; ++l) {
     const int K = p.a.L[l].in;
     const bool vw = K % 4 == 0;
@@ -986,14 +1027,18 @@ int headb_fwd(int nl, const int* dims, const int* flags, const float* drops, con
       hipLaunchKernelGGL(headb_ln_fwd_kernel, dim3((B + BNT / 64 - 1) / (BNT / 64)), dim3(BNT), 0,
                          st, p.a, l, (char*)ws);
   }
-  hipLaunchKernelGGL(headb_loss_kernel, dim3(1), dim3(LOSS_NT), 0, st, p.a, y, out, loss, pred,
-                     rng, (char*)ws);
+  if (lossp)
+    hipLaunchKernelGGL(headb_loss_kernel<true>, dim3(1), dim3(LOSS_NT), 0, st, p.a, y, out, loss,
+                       pred, rng, (char*)ws, lossp);
+  else
+    hipLaunchKernelGGL(headb_loss_kernel<false>, dim3(1), dim3(LOSS_NT), 0, st, p.a, y, out, loss,
+                       pred, rng, (char*)ws, lossp);
   return dn_launch_status();
 }
 
 int headb_bwd(int nl, const int* dims, const int* flags, const float* drops, const float* bnp,
               void* const* ptrs, int B, void* ws, const float* dloss, float* dx, long lddx,
-              hipStream_t st) {
+              int lw, hipStream_t st) {
   BPlan p;
   if (!bplan(nl, dims, flags, drops, bnp, ptrs, B, p)) return DN_UNSUPPORTED;
   for (int l = 0; l < nl; ++l) {
@@ -1034,11 +1079,11 @@ int headb_bwd(int nl, const int* dims, const int* flags, const float* drops, con
     const RedJob rj = take(nA + nW, g);
     const dim3 grid(g);
     if (l == nl - 1) {
-      if (vw) hipLaunchKernelGGL((headb_bwd_kernel<true, true>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj);
-      else hipLaunchKernelGGL((headb_bwd_kernel<true, false>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj);
+      if (vw) hipLaunchKernelGGL((headb_bwd_kernel<true, true>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj, lw);
+      else hipLaunchKernelGGL((headb_bwd_kernel<true, false>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj, lw);
     } else {
-      if (vw) hipLaunchKernelGGL((headb_bwd_kernel<false, true>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj);
-      else hipLaunchKernelGGL((headb_bwd_kernel<false, false>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj);
+      if (vw) hipLaunchKernelGGL((headb_bwd_kernel<false, true>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj, lw);
+      else hipLaunchKernelGGL((headb_bwd_kernel<false, false>), grid, dim3(BNT), 0, st, p.a, l, (char*)ws, dloss, dx, lddx, nA, RS, rj, lw);
     }
     if (RS > 1) {
       const long NK = (long)L.out * L.in;

@@ -106,7 +106,7 @@ int headb_layout(int nl, const int* dims, const int* flags, int B, long* out);
 int headb_fwd(int nl, const int* dims, const int* flags, const float* drops, const float* bnp,
               void* const* ptrs, const float* x, long ldx, int B, const long long* y, float* out,
               float* loss, long long* pred, unsigned long long* rng, void* ws, int train,
-              int log_out, hipStream_t st);
+              int log_out, const float* lossp, hipStream_t st);
 int headb_bwd(int nl, const int* dims, const int* flags, const float* drops, const float* bnp,
               void* const* ptrs, int B, void* ws, const float* dloss, float* dx, long lddx,
-              hipStream_t st);
+              int lw, hipStream_t st);

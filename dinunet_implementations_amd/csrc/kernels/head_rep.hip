@@ -37,6 +37,7 @@
 // back mean / rstd -- four workgroup barriers forward, two backward, xhat still in the owning
 // wave's registers.  Reduction orders and roundings are the shared ones of head_common.h.
 #include "head_common.h"
+#include "loss_opt.h"
 #include <stdlib.h>
 
 namespace {
@@ -113,12 +114,15 @@ __device__ __forceinline__ void warm_rep_kernargs() {
   asm volatile("" ::"s"(acc));
 }
 
+// LW: the loss options are on (lossp: the block of loss_opt.h, 16 weight slots readable); the
+// LW = false instantiation is the plain mean cross-entropy, unchanged.
+template <bool LW>
 __global__ void __launch_bounds__(RNT)
 head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long long* __restrict__ y,
                 float* __restrict__ out, float* __restrict__ loss, long long* __restrict__ pred,
                 unsigned long long* __restrict__ rng, const float* __restrict__ dloss,
                 float* __restrict__ dx, long lddx, unsigned* __restrict__ sync,
-                unsigned long long* __restrict__ stamps) {
+                unsigned long long* __restrict__ stamps, const float* __restrict__ lossp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   warm_rep_kernargs();
   const int tid = threadIdx.x, lane = tid & 63, wid = uni(tid >> 6);
@@ -542,10 +546,29 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
     int yc = mv ? ylds[m & (RMP - 1)] : 0;
     yc = yc < 0 ? 0 : (yc >= C ? C - 1 : yc);
     float pr[16], dv[16];
+    // loss options: the same arithmetic, in the same order, as the three-launch head's loss
+    // (mlp_head.hip fwd1): D = sum_i w[y_i] by the wave butterfly, lane = row
+    LossOpt lo{1.f, 0.f, 0.f};
+    float D = (float)B, awy = 0.f, S = 0.f;
+    if constexpr (LW) {
+      lo = lo_load(lossp);
+      const float wy = mv ? lossp[DN_LOSS_W0 + yc] : 0.f;
+      D = wy;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) D += __shfl_xor(D, off);
+      awy = lo_mul(lo.a, wy);
+    }
+    const float coef = awy + lo.eW;
 #pragma unroll
     for (int cc = 0; cc < 16; ++cc) {
       pr[cc] = expf(lg[cc] - lse);
-      dv[cc] = (mv && cc < C) ? (pr[cc] - (cc == yc ? 1.f : 0.f)) / (float)B : 0.f;
+      if constexpr (LW) {
+        const float wc = lossp[DN_LOSS_W0 + cc];
+        dv[cc] = (mv && cc < C) ? lo_grad(pr[cc], cc == yc, awy, coef, lo_mul(lo.e, wc)) / D : 0.f;
+        if (cc < C) S += lo_mul(wc, lse - lg[cc]);
+      } else {
+        dv[cc] = (mv && cc < C) ? (pr[cc] - (cc == yc ? 1.f : 0.f)) / (float)B : 0.f;
+      }
     }
     if (lane < RMP) {
       f32x4* d4 = reinterpret_cast<f32x4*>(dr);
@@ -577,11 +600,12 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
         }
       }
       float ls = mv ? lse - ly : 0.f;
+      if constexpr (LW) ls = mv ? lo_row(lo, awy, lse - ly, S) : 0.f;
       if (mv) pred[m] = am;
 #pragma unroll
       for (int off = 32; off >= 1; off >>= 1) ls += __shfl_xor(ls, off);
       if (lane == 0) {
-        *loss = ls / (float)B;
+        *loss = ls / D;
         for (int l = 0; l < nl; ++l)
           if (a.L[l].bn == 2 && a.L[l].nbt)
             __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(a.L[l].nbt), 1ull,
@@ -1083,12 +1107,13 @@ static unsigned long long* g_rep_stamps = nullptr;
 // table of this geometry in device memory (dn_head_rep_jobs).  sync: the head's
 // control block (dn_head_rep_sync_bytes(), zeroed before first use).  DN_UNSUPPORTED outside the
 // envelope (rep_plan).
-DN_API int dn_head_rep(int nl, const int* dims, const int* flags, const float* drops,
-                       const float* bnp, void* const* ptrs, void* const* wbf, const int* jtab,
-                       const float* x,
-                       long ldx, int B, const long long* y, float* out, float* loss,
-                       long long* pred, unsigned long long* rng, void* sync, int log_out,
-                       const float* dloss, float* dx, long lddx, hipStream_t st) {
+// lossp: the loss-option block of loss_opt.h (all 16 weight slots allocated), null = off.
+DN_API int dn_head_rep_lw(int nl, const int* dims, const int* flags, const float* drops,
+                          const float* bnp, void* const* ptrs, void* const* wbf, const int* jtab,
+                          const float* x, long ldx, int B, const long long* y, float* out,
+                          float* loss, long long* pred, unsigned long long* rng, void* sync,
+                          int log_out, const float* dloss, float* dx, long lddx,
+                          const float* lossp, hipStream_t st) {
   RPlan p;
   if (!dloss || !sync || !rng || !wbf || !rep_plan(nl, dims, flags, drops, bnp, ptrs, wbf, B, p))
     return DN_UNSUPPORTED;
@@ -1096,7 +1121,9 @@ DN_API int dn_head_rep(int nl, const int* dims, const int* flags, const float* d
   p.a.jtab = jtab;
   if ((((uintptr_t)x) & 15) || ldx % 4) return DN_UNSUPPORTED;
   if (!g_rep_init) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_rep_kernel),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_rep_kernel<false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_rep_kernel<true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     g_rep_init = true;
   }
@@ -1107,9 +1134,23 @@ DN_API int dn_head_rep(int nl, const int* dims, const int* flags, const float* d
     const int k = atoi(e);
     if (k > 0 && k < p.a.G) p.a.G = k;
   }
-  hipLaunchKernelGGL(head_rep_kernel, dim3(p.a.G), dim3(RNT), p.lds, st, p.a, x, ldx, y, out,
-                     loss, pred, rng, dloss, dx, lddx, (unsigned*)sync, g_rep_stamps);
+  if (lossp)
+    hipLaunchKernelGGL(head_rep_kernel<true>, dim3(p.a.G), dim3(RNT), p.lds, st, p.a, x, ldx, y,
+                       out, loss, pred, rng, dloss, dx, lddx, (unsigned*)sync, g_rep_stamps, lossp);
+  else
+    hipLaunchKernelGGL(head_rep_kernel<false>, dim3(p.a.G), dim3(RNT), p.lds, st, p.a, x, ldx, y,
+                       out, loss, pred, rng, dloss, dx, lddx, (unsigned*)sync, g_rep_stamps, lossp);
   return dn_launch_status();
+}
+
+DN_API int dn_head_rep(int nl, const int* dims, const int* flags, const float* drops,
+                       const float* bnp, void* const* ptrs, void* const* wbf, const int* jtab,
+                       const float* x,
+                       long ldx, int B, const long long* y, float* out, float* loss,
+                       long long* pred, unsigned long long* rng, void* sync, int log_out,
+                       const float* dloss, float* dx, long lddx, hipStream_t st) {
+  return dn_head_rep_lw(nl, dims, flags, drops, bnp, ptrs, wbf, jtab, x, ldx, B, y, out, loss,
+                        pred, rng, sync, log_out, dloss, dx, lddx, nullptr, st);
 }
 
 // Phase stamps of workgroup 0 (s_memrealtime, 100 MHz) into p[0..15]; null turns them off

@@ -37,6 +37,7 @@
 // tile.  Every reduction has a fixed order (head_common.h, shared with head_rep.hip so the
 // one-launch head agrees bitwise): two runs are bitwise equal.
 #include "head_common.h"
+#include "loss_opt.h"
 
 namespace {
 
@@ -560,8 +561,11 @@ head_fwd0_kernel(HArgs a, const float* __restrict__ x, long ldx,
 // fwd1: layers 1.. and the loss in one workgroup.
 // dzl_lds (fused fwd1+bwd1 only): d loss / d logits also parked in LDS for the backward chain.
 // Returns the dropout seed of this forward.
-template <int MT, bool VECW>
-__device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const long long* __restrict__ y,
+// LW: the loss options are on (lossp: the block of loss_opt.h); the LW = false instantiations are
+// the plain mean cross-entropy, unchanged.
+template <int MT, bool VECW, bool LW>
+__device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const float* __restrict__ lossp,
+                                              const long long* __restrict__ y,
                                               float* __restrict__ out, float* __restrict__ loss,
                                               long long* __restrict__ pred,
                                               unsigned long long* __restrict__ rng,
@@ -656,6 +660,20 @@ __device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const long long* _
     const int C = a.L[a.nl - 1].out;
     const int m = lane;
     float ls = 0.f;
+    // loss options: D = sum_i w[y_i] over the wave (lane = row), the same butterfly as the loss
+    LossOpt lo{1.f, 0.f, 0.f};
+    float wy = 0.f, D = (float)B;
+    if constexpr (LW) {
+      lo = lo_load(lossp);
+      if (m < B) {
+        long long yc = MT <= 2 ? (long long)ylds[m] : y[m];
+        yc = yc < 0 ? 0 : (yc >= C ? C - 1 : yc);
+        wy = lossp[DN_LOSS_W0 + yc];
+      }
+      D = wy;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) D += __shfl_xor(D, off);
+    }
     if (m < B) {
       float mx = -INFINITY;
       int am = 0;
@@ -669,21 +687,31 @@ __device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const long long* _
       long long yc = MT <= 2 ? (long long)ylds[m] : y[m];
       yc = yc < 0 ? 0 : (yc >= C ? C - 1 : yc);
       float* dzl = reinterpret_cast<float*>(ws + a.dzl_off);
+      const float awy = lo_mul(lo.a, wy), coef = awy + lo.eW;
+      float S = 0.f;
       for (int c = 0; c < C; ++c) {
         const float lp = logit[m * 16 + c] - lse;
         const float p = expf(lp);
         out[(long)m * C + c] = a.log_out ? lp : p;
-        const float dl = (p - (c == yc ? 1.f : 0.f)) / (float)B;
+        float dl;
+        if constexpr (LW) {
+          const float wc = lossp[DN_LOSS_W0 + c];
+          dl = lo_grad(p, c == yc, awy, coef, lo_mul(lo.e, wc)) / D;
+          S += lo_mul(wc, lse - logit[m * 16 + c]);
+        } else {
+          dl = (p - (c == yc ? 1.f : 0.f)) / (float)B;
+        }
         if (train) dzl[m * 16 + c] = dl;
         if (dzl_lds) dzl_lds[m * 16 + c] = dl;
       }
       ls = lse - logit[m * 16 + yc];
+      if constexpr (LW) ls = lo_row(lo, awy, ls, S);
       pred[m] = am;
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) ls += __shfl_xor(ls, off);
     if (lane == 0) {
-      *loss = ls / (float)B;
+      *loss = ls / D;
       if (train) {
         *reinterpret_cast<unsigned long long*>(ws) = seed;
         if (rng) *rng = seed + 1ull;
@@ -699,14 +727,14 @@ __device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const long long* _
   return seed;
 }
 
-template <int MT, bool VECW>
+template <int MT, bool VECW, bool LW>
 __global__ void __launch_bounds__(HS_NT)
 head_fwd1_kernel(HArgs a, const long long* __restrict__ y, float* __restrict__ out,
                  float* __restrict__ loss, long long* __restrict__ pred,
                  unsigned long long* __restrict__ rng, char* __restrict__ ws,
-                 unsigned long long* __restrict__ stamps) {
+                 unsigned long long* __restrict__ stamps, const float* __restrict__ lossp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  fwd1_body<MT, VECW>(a, y, out, loss, pred, rng, ws, stamps, smem);
+  fwd1_body<MT, VECW, LW>(a, lossp, y, out, loss, pred, rng, ws, stamps, smem);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -942,17 +970,18 @@ head_bwd1_kernel(HArgs a, char* __restrict__ ws, const float* __restrict__ dloss
 // Training step whose d loss is known at forward time (a persistent 1 the step's backward
 // passes): fwd1 and bwd1 in ONE single-workgroup launch, so the output-gradient chain starts
 // without a kernel boundary and on an L2-hot workspace.
-template <int MT, bool VECW>
+template <int MT, bool VECW, bool LW>
 __global__ void __launch_bounds__(HS_NT)
 head_fwd1_bwd1_kernel(HArgs a, const long long* __restrict__ y, float* __restrict__ out,
                       float* __restrict__ loss, long long* __restrict__ pred,
                       unsigned long long* __restrict__ rng, char* __restrict__ ws,
                       const float* __restrict__ dloss, unsigned long long* __restrict__ stamps,
-                      int dzl_lds_off) {
+                      int dzl_lds_off, const float* __restrict__ lossp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const float gs = *dloss;  // requested now: used after the whole forward half
   float* dzl_lds = reinterpret_cast<float*>(smem + dzl_lds_off);  // clear of both halves' LDS
-  const uint64_t seed = fwd1_body<MT, VECW>(a, y, out, loss, pred, rng, ws, stamps, smem, dzl_lds);
+  const uint64_t seed = fwd1_body<MT, VECW, LW>(a, lossp, y, out, loss, pred, rng, ws, stamps, smem,
+                                                dzl_lds);
   __threadfence_block();
   __syncthreads();
   const Bwd1Pre pre{gs, seed, dzl_lds};
@@ -1103,6 +1132,7 @@ struct Plan {
   int grid_fwd0, grid_bwd0_dw, grid_bwd0_dx;
   long lds_fwd0, lds_fwd1, lds_bwd1, lds_bwd0;
   long lds_fused_base, lds_fused;  // fused fwd1+bwd1: both halves, then d loss / d logits
+  const float* lossp = nullptr;    // loss options of this launch (loss_opt.h), null = off
 };
 
 static long al256(long v) { return (v + 255) & ~255L; }
@@ -1213,16 +1243,22 @@ static void head_init() {
   allow_lds(head_fwd0_kernel<2, false>);
   allow_lds(head_fwd0_kernel<4, true>);
   allow_lds(head_fwd0_kernel<4, false>);
-  allow_lds(head_fwd1_kernel<2, true>);
-  allow_lds(head_fwd1_kernel<2, false>);
-  allow_lds(head_fwd1_kernel<4, true>);
-  allow_lds(head_fwd1_kernel<4, false>);
+  allow_lds(head_fwd1_kernel<2, true, false>);
+  allow_lds(head_fwd1_kernel<2, false, false>);
+  allow_lds(head_fwd1_kernel<4, true, false>);
+  allow_lds(head_fwd1_kernel<4, false, false>);
+  allow_lds(head_fwd1_kernel<2, true, true>);
+  allow_lds(head_fwd1_kernel<2, false, true>);
+  allow_lds(head_fwd1_kernel<4, true, true>);
+  allow_lds(head_fwd1_kernel<4, false, true>);
   allow_lds(head_bwd1_kernel<2>);
   allow_lds(head_bwd1_kernel<4>);
   allow_lds(head_bwd0_kernel<2>);
   allow_lds(head_bwd0_kernel<4>);
-  allow_lds(head_fwd1_bwd1_kernel<2, true>);
-  allow_lds(head_fwd1_bwd1_kernel<2, false>);
+  allow_lds(head_fwd1_bwd1_kernel<2, true, false>);
+  allow_lds(head_fwd1_bwd1_kernel<2, false, false>);
+  allow_lds(head_fwd1_bwd1_kernel<2, true, true>);
+  allow_lds(head_fwd1_bwd1_kernel<2, false, true>);
   g_head_init = true;
 }
 
@@ -1235,15 +1271,24 @@ static void launch_fwd_t(const Plan& p, const float* x, long ldx, const long lon
   // (no fused variant for 64-row batches: the bwd1 phase spills at MT = 4)
   if constexpr (MT == 2) {
     if (dloss) {
-      hipLaunchKernelGGL((head_fwd1_bwd1_kernel<MT, V1>), dim3(1), dim3(HS_NT), p.lds_fused, st,
-                         p.a, y, out, loss, pred, rng, (char*)ws, dloss, g_head_stamps,
-                         (int)p.lds_fused_base);
+      if (p.lossp)
+        hipLaunchKernelGGL((head_fwd1_bwd1_kernel<MT, V1, true>), dim3(1), dim3(HS_NT),
+                           p.lds_fused, st, p.a, y, out, loss, pred, rng, (char*)ws, dloss,
+                           g_head_stamps, (int)p.lds_fused_base, p.lossp);
+      else
+        hipLaunchKernelGGL((head_fwd1_bwd1_kernel<MT, V1, false>), dim3(1), dim3(HS_NT),
+                           p.lds_fused, st, p.a, y, out, loss, pred, rng, (char*)ws, dloss,
+                           g_head_stamps, (int)p.lds_fused_base, p.lossp);
       return;
     }
   }
   {
-    hipLaunchKernelGGL((head_fwd1_kernel<MT, V1>), dim3(1), dim3(HS_NT), p.lds_fwd1, st, p.a, y,
-                       out, loss, pred, rng, (char*)ws, g_head_stamps);
+    if (p.lossp)
+      hipLaunchKernelGGL((head_fwd1_kernel<MT, V1, true>), dim3(1), dim3(HS_NT), p.lds_fwd1, st,
+                         p.a, y, out, loss, pred, rng, (char*)ws, g_head_stamps, p.lossp);
+    else
+      hipLaunchKernelGGL((head_fwd1_kernel<MT, V1, false>), dim3(1), dim3(HS_NT), p.lds_fwd1, st,
+                         p.a, y, out, loss, pred, rng, (char*)ws, g_head_stamps, p.lossp);
   }
 }
 
@@ -1291,18 +1336,21 @@ DN_API int dn_head_layout(int nl, const int* dims, const int* flags, int B, long
 
 // ptrs: 11 per layer {W, b, gamma, beta, running_mean, running_var, num_batches_tracked,
 //                     gW, gb, ggamma, gbeta} (null where absent; grads only for the backward)
-DN_API int dn_head_fwd(int nl, const int* dims, const int* flags, const float* drops,
-                       const float* bnp, void* const* ptrs, const float* x, long ldx, int B,
-                       const long long* y, float* out, float* loss, long long* pred,
-                       unsigned long long* rng, void* ws, int train, int log_out, hipStream_t st) {
+// lossp: the loss-option block of loss_opt.h (device memory, <= 16 class weights), null = off.
+DN_API int dn_head_fwd_lw(int nl, const int* dims, const int* flags, const float* drops,
+                          const float* bnp, void* const* ptrs, const float* x, long ldx, int B,
+                          const long long* y, float* out, float* loss, long long* pred,
+                          unsigned long long* rng, void* ws, int train, int log_out,
+                          const float* lossp, hipStream_t st) {
   if (B > 64)
     return headb_fwd(nl, dims, flags, drops, bnp, ptrs, x, ldx, B, y, out, loss, pred, rng, ws,
-                     train, log_out, st);
+                     train, log_out, lossp, st);
   Plan p;
   if (!make_plan(nl, dims, flags, drops, bnp, ptrs, B, p)) return DN_UNSUPPORTED;
   head_init();
   p.a.train = train;
   p.a.log_out = log_out;
+  p.lossp = lossp;
   if (p.Mp == 32)
     launch_fwd<2>(p, x, ldx, y, out, loss, pred, rng, ws, nullptr, st);
   else
@@ -1310,15 +1358,23 @@ DN_API int dn_head_fwd(int nl, const int* dims, const int* flags, const float* d
   return dn_launch_status();
 }
 
+DN_API int dn_head_fwd(int nl, const int* dims, const int* flags, const float* drops,
+                       const float* bnp, void* const* ptrs, const float* x, long ldx, int B,
+                       const long long* y, float* out, float* loss, long long* pred,
+                       unsigned long long* rng, void* ws, int train, int log_out, hipStream_t st) {
+  return dn_head_fwd_lw(nl, dims, flags, drops, bnp, ptrs, x, ldx, B, y, out, loss, pred, rng, ws,
+                        train, log_out, nullptr, st);
+}
+
 // Training forward that also runs the output-gradient chain (bwd1) for the d loss already held
 // at `dloss` (the step's persistent 1): ptrs must carry the gradient buffers; the bias /
 // BatchNorm gradients wait in the workspace stash until dn_head_bwd0 (apply_stash = 1) adds
 // them, so a backward with a different d loss can still run the full dn_head_bwd instead.
-DN_API int dn_head_fwd_train(int nl, const int* dims, const int* flags, const float* drops,
-                             const float* bnp, void* const* ptrs, const float* x, long ldx, int B,
-                             const long long* y, float* out, float* loss, long long* pred,
-                             unsigned long long* rng, void* ws, int log_out, const float* dloss,
-                             hipStream_t st) {
+DN_API int dn_head_fwd_train_lw(int nl, const int* dims, const int* flags, const float* drops,
+                                const float* bnp, void* const* ptrs, const float* x, long ldx,
+                                int B, const long long* y, float* out, float* loss,
+                                long long* pred, unsigned long long* rng, void* ws, int log_out,
+                                const float* dloss, const float* lossp, hipStream_t st) {
   Plan p;
   if (!dloss || !make_plan(nl, dims, flags, drops, bnp, ptrs, B, p)) return DN_UNSUPPORTED;
   if (p.Mp != 32) return DN_UNSUPPORTED;  // B <= 32 only; the caller runs dn_head_fwd instead
@@ -1329,11 +1385,21 @@ DN_API int dn_head_fwd_train(int nl, const int* dims, const int* flags, const fl
   head_init();
   p.a.train = 1;
   p.a.log_out = log_out;
+  p.lossp = lossp;
   if (p.Mp == 32)
     launch_fwd<2>(p, x, ldx, y, out, loss, pred, rng, ws, dloss, st);
   else
     launch_fwd<4>(p, x, ldx, y, out, loss, pred, rng, ws, dloss, st);
   return dn_launch_status();
+}
+
+DN_API int dn_head_fwd_train(int nl, const int* dims, const int* flags, const float* drops,
+                             const float* bnp, void* const* ptrs, const float* x, long ldx, int B,
+                             const long long* y, float* out, float* loss, long long* pred,
+                             unsigned long long* rng, void* ws, int log_out, const float* dloss,
+                             hipStream_t st) {
+  return dn_head_fwd_train_lw(nl, dims, flags, drops, bnp, ptrs, x, ldx, B, y, out, loss, pred,
+                              rng, ws, log_out, dloss, nullptr, st);
 }
 
 // The rest of the backward after dn_head_fwd_train: dW of every layer, dX, and the stashed bias
@@ -1362,10 +1428,11 @@ DN_API int dn_head_bwd0(int nl, const int* dims, const int* flags, const float* 
 
 // Backward of a training-mode dn_head_fwd on the same workspace; dloss: device scalar d out/d loss;
 // dx (may be null): d loss / d x, row stride lddx.
-DN_API int dn_head_bwd(int nl, const int* dims, const int* flags, const float* drops,
-                       const float* bnp, void* const* ptrs, int B, void* ws, const float* dloss,
-                       float* dx, long lddx, hipStream_t st) {
-  if (B > 64) return headb_bwd(nl, dims, flags, drops, bnp, ptrs, B, ws, dloss, dx, lddx, st);
+// lw: the forward on this workspace ran with the loss options on (dn_head_fwd_lw with a block).
+DN_API int dn_head_bwd_lw(int nl, const int* dims, const int* flags, const float* drops,
+                          const float* bnp, void* const* ptrs, int B, void* ws, const float* dloss,
+                          float* dx, long lddx, int lw, hipStream_t st) {
+  if (B > 64) return headb_bwd(nl, dims, flags, drops, bnp, ptrs, B, ws, dloss, dx, lddx, lw, st);
   Plan p;
   if (!make_plan(nl, dims, flags, drops, bnp, ptrs, B, p)) return DN_UNSUPPORTED;
   for (int l = 0; l < nl; ++l) {
@@ -1388,4 +1455,10 @@ DN_API int dn_head_bwd(int nl, const int* dims, const int* flags, const float* d
                        (const char*)ws, dx, lddx, 0, g_head_stamps);
   }
   return dn_launch_status();
+}
+
+DN_API int dn_head_bwd(int nl, const int* dims, const int* flags, const float* drops,
+                       const float* bnp, void* const* ptrs, int B, void* ws, const float* dloss,
+                       float* dx, long lddx, hipStream_t st) {
+  return dn_head_bwd_lw(nl, dims, flags, drops, bnp, ptrs, B, ws, dloss, dx, lddx, 0, st);
 }

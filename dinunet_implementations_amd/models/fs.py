@@ -9,6 +9,11 @@ The BatchNorm never tracks running statistics, so evaluation also uses batch sta
 On a GPU ``forward_loss`` runs the whole network + log-softmax/NLL as one fused HIP launch
 forward and one backward (``ops.head``); the module tree is kept for parameter ownership,
 checkpoint compatibility, the CPU oracle path and ``forward`` (logits).
+
+``class_weights`` (one finite number > 0 per class) and ``label_smoothing`` (``[0, 1)``) make
+every loss path compute ``F.cross_entropy(logits, y, weight=..., label_smoothing=...)``, each
+batch normalised by its own ``sum_i weight[y_i]`` (``ops.head``).  They are plain attributes
+of the head spec, not ``state_dict`` entries; :meth:`set_loss` changes their values in place.
 """
 from __future__ import annotations
 
@@ -22,8 +27,10 @@ from .. import ops
 
 class MSANNet(nn.Module):
     def __init__(self, in_size: int, hidden_sizes: Sequence[int], out_size: int,
-                 dropout_in: Sequence[int] = (), norm_layer: str = "batch"):
+                 dropout_in: Sequence[int] = (), norm_layer: str = "batch",
+                 class_weights=None, label_smoothing: float = 0.0):
         super().__init__()
+        self._loss_opts = ops.check_loss_options(class_weights, label_smoothing, int(out_size))
         self.in_size = int(in_size)
         self.out_size = int(out_size)
         self.hidden_sizes = [int(h) for h in hidden_sizes]
@@ -49,8 +56,12 @@ class MSANNet(nn.Module):
     def head_spec(self) -> "ops.HeadSpec":
         if self._head is None:
             mods = [m for blk in self.layers for m in blk] + [self.fc_out]
-            self._head = ops.HeadSpec(mods)
+            self._head = ops.HeadSpec(mods, *self._loss_opts)
         return self._head
+
+    def set_loss(self, class_weights=None, label_smoothing=None):
+        """New loss-option values in place (``ops.HeadSpec.set_loss``; captured graphs follow)."""
+        self.head_spec().set_loss(class_weights, label_smoothing)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         for layer in self.layers:
@@ -58,8 +69,10 @@ class MSANNet(nn.Module):
         return self.fc_out(x)
 
     def forward_loss(self, x: torch.Tensor, y: torch.Tensor):
-        """``(log_probs, nll_loss, argmax)`` (reference ``comps/fs/__init__.py:54-57``)."""
+        """``(log_probs, nll_loss, argmax)`` (reference ``comps/fs/__init__.py:54-57``).  With
+        class weights or label smoothing the loss is the weighted / smoothed cross-entropy of the
+        logits (torch's ``nll_loss`` has no smoothing argument); the log-probabilities stay."""
         if self.use_fused and x.is_cuda:
             return ops.head_loss(x, self.head_spec(), y, log_out=True)
         logits = self.forward(x)
-        return ops.log_softmax_nll(logits, y)
+        return ops.log_softmax_nll(logits, y, **self.head_spec().loss_kwargs(logits.device))

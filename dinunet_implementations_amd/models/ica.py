@@ -134,8 +134,13 @@ class ICALstm(nn.Module):
 
     def __init__(self, input_size: int = 256, hidden_size: int = 256, bidirectional: bool = True,
                  num_cls: int = 2, num_comps: int = 53, window_size: int = 20,
-                 num_layers: int = 1, norm_layer: str = "batch"):
+                 num_layers: int = 1, norm_layer: str = "batch", class_weights=None,
+                 label_smoothing: float = 0.0):
         super().__init__()
+        # loss options (ops.head): F.cross_entropy's weight / label_smoothing, every batch
+        # normalised by its own sum_i weight[y_i]; attributes of the head spec, not state_dict
+        # entries (the key set stays the reference's)
+        self._loss_opts = ops.check_loss_options(class_weights, label_smoothing, int(num_cls))
         self.input_size = input_size
         self.hidden_size = hidden_size
         self.num_comp = num_comps
@@ -162,8 +167,12 @@ class ICALstm(nn.Module):
 
     def head_spec(self) -> "ops.HeadSpec":
         if self._head is None:
-            self._head = ops.HeadSpec(list(self.classifier))
+            self._head = ops.HeadSpec(list(self.classifier), *self._loss_opts)
         return self._head
+
+    def set_loss(self, class_weights=None, label_smoothing=None):
+        """New loss-option values in place (``ops.HeadSpec.set_loss``; captured graphs follow)."""
+        self.head_spec().set_loss(class_weights, label_smoothing)
 
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         """``[B, S, C, W] -> [B, S, I]``: one batched GEMM instead of the per-sample loop."""
@@ -251,7 +260,7 @@ class ICALstm(nn.Module):
         o = o.flatten(1).to(self.classifier[1].weight.dtype)
         if self.use_fused and o.is_cuda:
             return ops.head_loss(o, self.head_spec(), y, log_out=False)
-        return ops.softmax_ce(self.classifier(o), y)
+        return ops.softmax_ce(self.classifier(o), y, **self.head_spec().loss_kwargs(o.device))
 
     def persistent_pack(self, device) -> Optional["ops.lstm.PersistentPack"]:
         """Step-persistent packed operands for a fused Adam that keeps them current
@@ -276,4 +285,4 @@ class ICALstm(nn.Module):
         if self.use_fused and o.is_cuda:
             return ops.head_loss(o, self.head_spec(), y, log_out=False)
         logits = self.classifier(o)
-        return ops.softmax_ce(logits, y)
+        return ops.softmax_ce(logits, y, **self.head_spec().loss_kwargs(logits.device))

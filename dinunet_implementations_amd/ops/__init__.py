@@ -8,7 +8,7 @@ from .lstm import bilstm as _bilstm_fused, lstm_supported, padded_hidden
 from .optim import (DeviceSource, FlatParams, FusedAdam, StepRecorder, cast_bf16_to_f32,
                     cast_f32_to_bf16, step_prologue)
 from .heads import softmax_ce, log_softmax_nll
-from .head import HeadSpec, head_loss
+from .head import HeadSpec, check_loss_options, head_loss
 from .layernorm import LayerNorm, layer_norm
 
 

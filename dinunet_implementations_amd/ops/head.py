@@ -40,10 +40,22 @@ dX over many workgroups); it scales by ``dloss`` on the device, accumulates ever
 gradient straight into its ``.grad`` (flat-buffer view) and returns ``d input``.  Dropout masks are not bit-identical to ``torch.nn.Dropout``'s generator
 stream (same distribution, independent draws); everything else matches the module math with
 bf16 MFMA operands and fp32 accumulation / statistics.
+
+Loss options: ``HeadSpec(modules, class_weights=w, label_smoothing=eps)`` makes every path
+compute ``F.cross_entropy(z, y, weight=w, label_smoothing=eps)`` (mean reduction) instead of the
+plain mean cross-entropy; the FS head (log-softmax + NLL) applies the same formula to its logits
+(torch's ``nll_loss`` has no smoothing argument).  Outputs, ``pred``, label clamping and dropout
+draws do not change.  The normalisation is per batch, as in torch: each call divides by its own
+``D = sum_i w[y_i]``, so micro-batches of an accumulated step and the shards of a multi-GPU site
+each normalise by their own ``D`` (torch's behaviour under DataParallel too).  The kernels read
+the options from a small fp32 device block the spec owns (``csrc/kernels/loss_opt.h``), so
+:meth:`HeadSpec.set_loss` takes effect in already captured graphs; whether the options are on at
+all is fixed when the spec is built.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import List, Optional, Sequence
 
 import torch
@@ -72,6 +84,16 @@ _lib.register("dn_cast_bf16_group", [_P, _P, _P, _lib.c_int, _P])
 _lib.register("dn_head_rep", [_lib.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _lib.c_long, _lib.c_int,
                               _P, _P, _P, _P, _P, _P, _lib.c_int, _P, _P, _lib.c_long, _P])
 _lib.register("dn_head_rep_jobs", [_lib.c_int, _P, _P, _lib.c_int, _P, _lib.c_int])
+# the same entry points with the loss-option block (null = off) ahead of the stream
+_lib.register("dn_head_fwd_lw", [_lib.c_int, _P, _P, _P, _P, _P, _P, _lib.c_long, _lib.c_int, _P,
+                                 _P, _P, _P, _P, _P, _lib.c_int, _lib.c_int, _P, _P])
+_lib.register("dn_head_fwd_train_lw", [_lib.c_int, _P, _P, _P, _P, _P, _P, _lib.c_long, _lib.c_int,
+                                       _P, _P, _P, _P, _P, _P, _lib.c_int, _P, _P, _P])
+_lib.register("dn_head_bwd_lw", [_lib.c_int, _P, _P, _P, _P, _P, _lib.c_int, _P, _P, _P,
+                                 _lib.c_long, _lib.c_int, _P])
+_lib.register("dn_head_rep_lw", [_lib.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _lib.c_long,
+                                 _lib.c_int, _P, _P, _P, _P, _P, _P, _lib.c_int, _P, _P,
+                                 _lib.c_long, _P, _P])
 
 # d(loss) tensor of the running training step, when the step will backpropagate exactly that
 # tensor (runtime.step.TrainStep's persistent 1): the forward then runs the head's output-gradient
@@ -138,10 +160,23 @@ class _Layer:
 class HeadSpec:
     """A fusable description of ``modules`` (run in order) followed by a loss."""
 
-    def __init__(self, modules: Sequence[nn.Module]):
+    def __init__(self, modules: Sequence[nn.Module], class_weights=None,
+                 label_smoothing: float = 0.0):
         self.modules = list(modules)
         self.layers: List[_Layer] = []
         self.ok = True
+        lins = [m for m in self.modules if isinstance(m, nn.Linear)]
+        self.num_class = lins[-1].out_features if lins else 0
+        # A/B switches, read only where the argument is unset (as DINUNET_MAX_GRAD_NORM is)
+        if class_weights is None and _os.environ.get("DINUNET_CLASS_WEIGHTS"):
+            class_weights = _env_numbers("DINUNET_CLASS_WEIGHTS")
+        if not label_smoothing and _os.environ.get("DINUNET_LABEL_SMOOTHING"):
+            label_smoothing = _env_numbers("DINUNET_LABEL_SMOOTHING")[0]
+        self.class_weights, self.label_smoothing = check_loss_options(
+            class_weights, label_smoothing or 0.0, self.num_class)
+        # on / off is fixed here (a null block pointer runs the kernels' original code)
+        self.loss_on = self.class_weights is not None or self.label_smoothing != 0.0
+        self._lossblk = {}  # device -> the kernels' option block
         pending = 0.0
         for m in self.modules:
             if isinstance(m, nn.Dropout):
@@ -320,11 +355,78 @@ class HeadSpec:
                 arr[11 * l + j] = None if t is None else t.data_ptr()
         return arr
 
+    # ---- loss options ------------------------------------------------------------------------
+    def set_loss(self, class_weights=None, label_smoothing=None):
+        """Rewrite the option values in place (None keeps the current one): every device block
+        keeps its address, so captured graphs compute the new objective from their next replay.
+        Raises if the spec was built with the options off."""
+        if not self.loss_on:
+            raise RuntimeError("HeadSpec.set_loss: the spec was built without loss options "
+                               "(pass class_weights / label_smoothing to the constructor)")
+        w, eps = check_loss_options(
+            self.class_weights if class_weights is None else class_weights,
+            self.label_smoothing if label_smoothing is None else label_smoothing, self.num_class)
+        self.class_weights, self.label_smoothing = w, eps
+        for blk in self._lossblk.values():
+            blk.copy_(self._loss_values())
+
+    def _loss_values(self) -> Tensor:
+        from .heads import loss_block_values
+        return loss_block_values(self.class_weights, self.label_smoothing, self.num_class)
+
+    def loss_block(self, device) -> Optional[Tensor]:
+        """The option block on ``device`` (created on first use), None with the options off."""
+        if not self.loss_on:
+            return None
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        blk = self._lossblk.get(device)
+        if blk is None:
+            blk = self._lossblk[device] = self._loss_values().to(device)
+        return blk
+
+    def loss_kwargs(self, device) -> dict:
+        """``weight`` / ``label_smoothing`` / ``block`` for ``ops.softmax_ce`` and
+        ``ops.log_softmax_nll`` on the module path (CPU: ``ops.reference``; GPU: the spec's own
+        block, so nothing is rebuilt per call)."""
+        if not self.loss_on:
+            return {}
+        from .heads import LOSS_W0
+        blk = self.loss_block(device)
+        return {"weight": blk[LOSS_W0:LOSS_W0 + self.num_class],
+                "label_smoothing": self.label_smoothing, "block": blk}
+
     # ---- unfused path -----------------------------------------------------------------------
     def run_modules(self, x: Tensor) -> Tensor:
         for m in self.modules:
             x = m(x)
         return x
+
+
+def _env_numbers(name: str) -> List[float]:
+    try:
+        return [float(v) for v in _os.environ[name].split(",")]
+    except ValueError:
+        raise ValueError(f"{name} must be a comma list of numbers, got {_os.environ[name]!r}")
+
+
+def check_loss_options(class_weights, label_smoothing, num_class: int):
+    """``(weights as a list of floats or None, eps)``; ValueError on anything else."""
+    eps = 0.0 if label_smoothing is None else label_smoothing
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing {label_smoothing!r}: expected a number in [0, 1)")
+    if class_weights is None:
+        return None, float(eps)
+    if isinstance(class_weights, Tensor):
+        class_weights = class_weights.detach().cpu().tolist()
+    if isinstance(class_weights, (str, bytes)) or not isinstance(class_weights, (list, tuple)):
+        raise ValueError(f"class_weights {class_weights!r}: expected a list of {num_class} numbers")
+    w = list(class_weights)
+    if (len(w) != num_class or any(isinstance(v, bool) or not isinstance(v, (int, float))
+                                   or not math.isfinite(v) or v <= 0 for v in w)):
+        raise ValueError(f"class_weights {class_weights!r}: expected {num_class} finite numbers > 0")
+    return [float(v) for v in w], float(eps)
 
 
 class _HeadFn(torch.autograd.Function):
@@ -344,6 +446,7 @@ class _HeadFn(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         pred = torch.empty(B, dtype=torch.long, device=x.device)
         rng = spec.rng(x.device)
+        lossp = _lib.ptr(spec.loss_block(x.device))
         ctx.hint_ptr = None
         ctx.step_dx = None
         ctx.one_launch = False
@@ -355,11 +458,11 @@ class _HeadFn(torch.autograd.Function):
         if wbf is not None:
             dx = (torch.empty(B, x.shape[1], dtype=torch.float32, device=x.device)
                   if ctx.needs_input_grad[0] else None)
-            rc = _lib.lib().dn_head_rep(
+            rc = _lib.lib().dn_head_rep_lw(
                 spec.nl, spec._dims, spec._flags, spec._drops, spec._bnp, spec.ptrs(True), wbf,
                 jt.data_ptr(), x.data_ptr(), x.stride(0), B, y.data_ptr(), out.data_ptr(), loss.data_ptr(),
                 pred.data_ptr(), rng.data_ptr(), spec.sync(x.device).data_ptr(), int(log_out),
-                hint.data_ptr(), _lib.ptr(dx), x.shape[1], _lib.stream())
+                hint.data_ptr(), _lib.ptr(dx), x.shape[1], lossp, _lib.stream())
             if rc == 0:
                 global REP_LAUNCHES
                 REP_LAUNCHES += 1
@@ -373,20 +476,20 @@ class _HeadFn(torch.autograd.Function):
             if rc != 3:
                 raise RuntimeError(f"dn_head_rep failed with status {rc}")
         if train and hint is not None:
-            rc = _lib.lib().dn_head_fwd_train(
+            rc = _lib.lib().dn_head_fwd_train_lw(
                 spec.nl, spec._dims, spec._flags, spec._drops, spec._bnp, spec.ptrs(True),
                 x.data_ptr(), x.stride(0), B, y.data_ptr(), out.data_ptr(), loss.data_ptr(),
                 pred.data_ptr(), rng.data_ptr(), ws.data_ptr(), int(log_out), hint.data_ptr(),
-                _lib.stream())
+                lossp, _lib.stream())
             if rc == 0:
                 ctx.hint_ptr = hint.data_ptr()
             elif rc != 3:  # 3 = unsupported shape: the classic launches below
                 raise RuntimeError(f"dn_head_fwd_train failed with status {rc}")
         if ctx.hint_ptr is None:
-            _lib.call("dn_head_fwd", spec.nl, spec._dims, spec._flags, spec._drops, spec._bnp,
+            _lib.call("dn_head_fwd_lw", spec.nl, spec._dims, spec._flags, spec._drops, spec._bnp,
                       spec.ptrs(False), x.data_ptr(), x.stride(0), B, y.data_ptr(),
                       out.data_ptr(), loss.data_ptr(), pred.data_ptr(), rng.data_ptr(),
-                      ws.data_ptr(), int(train), int(log_out), _lib.stream())
+                      ws.data_ptr(), int(train), int(log_out), lossp, _lib.stream())
         ctx.spec, ctx.B, ctx.D0, ctx.train = spec, B, x.shape[1], train
         ctx.ws = ws if train else None
         ctx.mark_non_differentiable(out, pred)
@@ -417,9 +520,9 @@ class _HeadFn(torch.autograd.Function):
                       spec.ptrs(True), B, ctx.ws.data_ptr(), _lib.ptr(dx), ctx.D0,
                       _lib.stream())
         else:
-            _lib.call("dn_head_bwd", spec.nl, spec._dims, spec._flags, spec._drops, spec._bnp,
+            _lib.call("dn_head_bwd_lw", spec.nl, spec._dims, spec._flags, spec._drops, spec._bnp,
                       spec.ptrs(True), B, ctx.ws.data_ptr(), dloss.data_ptr(), _lib.ptr(dx),
-                      ctx.D0, _lib.stream())
+                      ctx.D0, int(spec.loss_on), _lib.stream())
         params = spec.params()
         _grad.notify(params)
         if _cap.active() is not None:
@@ -447,7 +550,6 @@ def head_loss(x: Tensor, spec: HeadSpec, y: Tensor, log_out: bool):
             hint = None
         return _HeadFn.apply(x, y, spec, bool(log_out), hint, *spec.params())
     logits = spec.run_modules(x)
-    if logits.is_cuda:
-        from .heads import log_softmax_nll, softmax_ce
-        return (log_softmax_nll if log_out else softmax_ce)(logits, y)
-    return (ref.log_softmax_nll if log_out else ref.softmax_ce)(logits, y)
+    from .heads import log_softmax_nll, softmax_ce  # (CPU logits: ops.reference)
+    return (log_softmax_nll if log_out else softmax_ce)(
+        logits, y, **spec.loss_kwargs(logits.device))

@@ -96,18 +96,39 @@ def ica_windows(data: Tensor, window_size: int, window_stride: int, temporal_siz
     return data[:, :, idx].permute(0, 2, 1, 3).contiguous()
 
 
-def softmax_ce(logits: Tensor, labels: Tensor):
-    """Reference ICA loss head (``comps/icalstm/__init__.py:60-63``)."""
+def softmax_ce(logits: Tensor, labels: Tensor, weight: Optional[Tensor] = None,
+               label_smoothing: float = 0.0):
+    """Reference ICA loss head (``comps/icalstm/__init__.py:60-63``).  ``weight`` (per-class) and
+    ``label_smoothing`` are ``F.cross_entropy``'s, mean reduction: the batch's loss is divided by
+    ``sum_i weight[y_i]`` of that batch."""
     prob = torch.softmax(logits, 1)
-    loss = F.cross_entropy(logits, labels)
+    if weight is None and not label_smoothing:
+        loss = F.cross_entropy(logits, labels)
+    else:
+        loss = F.cross_entropy(logits, labels, weight=_loss_weight(weight, logits),
+                               label_smoothing=float(label_smoothing))
     return prob, loss, prob.argmax(1)
 
 
-def log_softmax_nll(logits: Tensor, labels: Tensor):
-    """Reference FS loss head (``comps/fs/__init__.py:54-57``)."""
+def log_softmax_nll(logits: Tensor, labels: Tensor, weight: Optional[Tensor] = None,
+                    label_smoothing: float = 0.0):
+    """Reference FS loss head (``comps/fs/__init__.py:54-57``).  With ``weight`` or
+    ``label_smoothing`` the loss is ``F.cross_entropy`` on the logits (``nll_loss(log_softmax(z))
+    == cross_entropy(z)``; torch's ``nll_loss`` has no smoothing argument); ``out`` stays the
+    log-probabilities."""
     out = F.log_softmax(logits, 1)
-    loss = F.nll_loss(out, labels)
+    if weight is None and not label_smoothing:
+        loss = F.nll_loss(out, labels)
+    else:
+        loss = F.cross_entropy(logits, labels, weight=_loss_weight(weight, logits),
+                               label_smoothing=float(label_smoothing))
     return out, loss, out.argmax(1)
+
+
+def _loss_weight(weight, logits: Tensor) -> Optional[Tensor]:
+    if weight is None:
+        return None
+    return torch.as_tensor(weight, dtype=logits.dtype, device=logits.device)
 
 
 def adam_(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, beta1: float = 0.9,

@@ -155,6 +155,21 @@ class FederatedSite:
         self.group.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         return int(t.item())
 
+    def _balanced_weights(self, y: torch.Tensor, num_class: int) -> List[float]:
+        """``class_weights="balanced"``: ``w_c = n_total / (C * n_c)`` (sklearn's "balanced") from
+        the label counts of every site's training split.  Each rank counts its own shard; one
+        all-reduce of ``num_class`` int64 counts sums them (replicas hold disjoint shards), so a
+        site shows the others nothing but its class histogram and all optimise one objective."""
+        counts = torch.bincount(y.detach().long().cpu().clamp(0, num_class - 1),
+                                minlength=num_class)[:num_class].to(torch.int64)
+        counts = counts.to(self.device)
+        self.group.all_reduce(counts)
+        n = [int(v) for v in counts.cpu().tolist()]
+        if min(n) == 0:  # the same counts everywhere: every rank raises
+            raise ValueError(f"class_weights='balanced': a class has no training sample on any "
+                             f"site (global label counts {n})")
+        return [sum(n) / (num_class * c) for c in n]
+
     def _datasets(self, split: Dict[str, List[Any]]) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
         """The site's splits on this process's device; with several processes per site
         (``group.replicas``) this replica's shard of each: rows ``replica::replicas`` of the
@@ -574,13 +589,34 @@ class FederatedSite:
             "split_sizes": {k: int(v[1].shape[0]) for k, v in data.items()},
             "device": str(self.device),
         }
+        last = os.path.join(fdir, "checkpoint_last.pt")
+        # a resumed or tested model continues the objective its checkpoint was trained with
+        saved = None
+        if cfg.get("mode") == "test":
+            saved = cfg.get("pretrained_path") or os.path.join(fdir, "checkpoint_best.pt")
+        elif cfg.get("resume") and os.path.exists(last):
+            saved = last
+        lo = None
+        if saved is not None and os.path.exists(saved):
+            lo = torch.load(saved, map_location="cpu", weights_only=True).get("loss_options")
+            if lo:
+                cfg = dict(cfg, class_weights=list(lo["class_weights"]),
+                           label_smoothing=lo["label_smoothing"])
         trainer = self.Trainer(cache=cfg, state=self.state, device=self.device)
         trainer.init_nn(seed=int(cfg.get("seed", 0) or 0) + fold)  # same init on every site
+        if cfg.get("class_weights") == "balanced":
+            # before the first step and before any capture; pretraining, validation and test
+            # use the same weights
+            trainer.set_loss_options(self._balanced_weights(
+                data["train"][1], int(cfg.get("num_class", 2))))
+        lo = trainer.loss_options()
+        if lo is not None:
+            logs["class_weights"] = lo["class_weights"]
+            logs["label_smoothing"] = lo["label_smoothing"]
         check_eval_batch_size(cfg, trainer)
         self._eval_feeds = {}  # (feeds hold the previous fold's trainer and splits)
         self._broadcast_model(trainer, 0)
         start_epoch, best, resume = 1, None, None
-        last = os.path.join(fdir, "checkpoint_last.pt")
         if cfg.get("mode") == "test":
             path = cfg.get("pretrained_path") or os.path.join(fdir, "checkpoint_best.pt")
             trainer.load_checkpoint(path)

@@ -84,6 +84,38 @@ class NNTrainer:
     def has_fast_path(self) -> bool:
         return type(self).forward_loss is not NNTrainer.forward_loss
 
+    # ---- loss options (ops.head: class weights / label smoothing) ------------------------------
+    def loss_option_args(self) -> Dict[str, Any]:
+        """Constructor arguments of the task's model from the cache keys ``class_weights`` /
+        ``label_smoothing``.  ``"balanced"`` builds the model with the options on and unit
+        weights; the site loop sets the resolved weights before the first step
+        (``runtime.site.FederatedSite``, :meth:`set_loss_options`)."""
+        cw = self.cache.get("class_weights")
+        if isinstance(cw, str):
+            if cw != "balanced":
+                raise ValueError(f"class_weights {cw!r}: expected a list, 'balanced' or None")
+            cw = [1.0] * int(self.cache.get("num_class", 2))
+        return {"class_weights": cw, "label_smoothing": self.cache.get("label_smoothing") or 0.0}
+
+    def _head_specs(self):
+        return [m.head_spec() for m in self.nn.values() if hasattr(m, "head_spec")]
+
+    def loss_options(self) -> Optional[Dict[str, Any]]:
+        """The resolved ``{"class_weights": [...], "label_smoothing": eps}`` the models train
+        with, or None when the options are off."""
+        for spec in self._head_specs():
+            if spec.loss_on:
+                w = spec.class_weights or [1.0] * spec.num_class
+                return {"class_weights": [float(v) for v in w],
+                        "label_smoothing": float(spec.label_smoothing)}
+        return None
+
+    def set_loss_options(self, class_weights=None, label_smoothing=None):
+        """New values in place (captured graphs follow; raises if the models were built with the
+        options off)."""
+        for spec in self._head_specs():
+            spec.set_loss(class_weights, label_smoothing)
+
     # ---- framework -----------------------------------------------------------------------------
     def new_metrics(self) -> Metrics:
         return Metrics(int(self.cache.get("num_class", 2)))
@@ -150,6 +182,9 @@ class NNTrainer:
                          for k, v in self.nn.items()}}
         if self.optimizer is not None:
             st["optimizer"] = self.optimizer.state_dict()
+        lo = self.loss_options()
+        if lo is not None:  # beside the model section: a resume / test continues the objective
+            st["loss_options"] = lo
         st.update(extra)
         return st
 
@@ -208,3 +243,6 @@ class NNTrainer:
                 self.nn[k].load_state_dict(sd)
         if load_optimizer and self.optimizer is not None and "optimizer" in st:
             self.optimizer.load_state_dict(st["optimizer"])
+        lo = st.get("loss_options")
+        if lo and self.loss_options() is not None:
+            self.set_loss_options(lo["class_weights"], lo["label_smoothing"])

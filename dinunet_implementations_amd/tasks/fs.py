@@ -95,7 +95,8 @@ class FreeSurferTrainer(NNTrainer):
                                     hidden_sizes=self.cache["hidden_sizes"],
                                     out_size=self.cache["num_class"],
                                     dropout_in=self.cache.get("dropout_in", []),
-                                    norm_layer=self.cache.get("norm_layer", "batch"))
+                                    norm_layer=self.cache.get("norm_layer", "batch"),
+                                    **self.loss_option_args())
 
     def forward_loss(self, x, y):
         return self.nn["fs_net"].forward_loss(x.float(), y)

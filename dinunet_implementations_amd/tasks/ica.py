@@ -98,7 +98,8 @@ class ICATrainer(NNTrainer):
                                  hidden_size=c["hidden_size"], num_comps=c["num_components"],
                                  num_cls=c["num_class"], num_layers=c.setdefault("num_layers", 1),
                                  bidirectional=c.setdefault("bidirectional", True),
-                                 norm_layer=c.get("norm_layer", "batch"))
+                                 norm_layer=c.get("norm_layer", "batch"),
+                                 **self.loss_option_args())
 
     def forward_loss(self, x, y):
         return self.nn["net"].forward_loss(x.float(), y)

@@ -5,7 +5,8 @@
 with the step's d-loss hint, as runtime.step runs it) per batch size in ``--batches``, with the
 norm chosen by ``--norm batch|layer``: eager wall time per step and GPU time per step from a
 replayed HIP graph of 20 steps, one JSON line per batch.  ``fused`` in the line says whether the
-fused head kernels took the head (false: the modules ran one by one).
+fused head kernels took the head (false: the modules ran one by one).  ``--class-weights w0 w1``
+and ``--label-smoothing eps`` time the same step with the loss options on.
 """
 import argparse
 import json
@@ -42,14 +43,15 @@ def _ica(norm, p):
                          nn.ReLU(), nn.Linear(64, 2))
 
 
-def step_bench(norm, batches, p=0.25, n=20):
+def step_bench(norm, batches, p=0.25, n=20, class_weights=None, label_smoothing=0.0):
     """One JSON line per batch: the hinted training step of the ICA head with ``norm``."""
     from dinunet_implementations_amd.ops import head as H
     dev = "cuda"
     for B in batches:
         torch.manual_seed(0)
         mods = _ica(norm, p).to(dev).train()
-        spec = H.HeadSpec(list(mods))
+        spec = H.HeadSpec(list(mods), class_weights=class_weights,
+                          label_smoothing=label_smoothing)
         x = torch.randn(B, 384, device=dev, requires_grad=True)
         y = torch.randint(0, 2, (B,), device=dev)
         one = torch.ones((), device=dev)
@@ -74,6 +76,8 @@ def step_bench(norm, batches, p=0.25, n=20):
                 step()
         gpu = t_us(g.replay, reps=20) / n
         print(json.dumps({"head": "ica", "norm": norm, "B": B, "dropout": p,
+                          "class_weights": spec.class_weights if spec.loss_on else None,
+                          "label_smoothing": spec.label_smoothing,
                           "fused": bool(spec.ok and spec.supported(x)), "one_launch": one_launch,
                           "step_gpu_us": round(gpu, 2), "step_wall_us": round(wall, 2)}))
 
@@ -85,9 +89,13 @@ def main():
     ap.add_argument("--step", action="store_true",
                     help="time the hinted training step per batch size (JSON lines) and exit")
     ap.add_argument("--batches", type=int, nargs="+", default=[32, 2048])
+    ap.add_argument("--class-weights", type=float, nargs=2, default=None,
+                    help="class weights of the loss (the two ICA classes); default: off")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
     args = ap.parse_args()
     if args.step:
-        step_bench(args.norm, args.batches)
+        step_bench(args.norm, args.batches, class_weights=args.class_weights,
+                   label_smoothing=args.label_smoothing)
         return
     from dinunet_implementations_amd.models import MSANNet
     from dinunet_implementations_amd.ops.head import HeadSpec
@@ -101,7 +109,8 @@ def main():
     cases.append(("FS MSANNet B=16", nn.Sequential(*[m for blk in fs.layers for m in blk], fs.fc_out), 16, 66, True))
     for name, mods, B, D, log_out in cases:
         mods = mods.to(dev).train()
-        spec = HeadSpec(list(mods))
+        spec = HeadSpec(list(mods), class_weights=args.class_weights,
+                        label_smoothing=args.label_smoothing)
         x = torch.randn(B, D, device=dev, requires_grad=True)
         y = torch.randint(0, 2, (B,), device=dev)
         holder = {}

@@ -29,7 +29,7 @@ from typing import Any, Dict, List, Optional
 
 import torch
 
-from ..config import build_config, site_seed
+from ..config import build_config, lr_schedule_of, site_seed
 from ..data.loader import DeviceLoader
 from ..data.splits import make_splits
 from ..parallel.engines import ENGINES
@@ -70,6 +70,16 @@ class LocalNode:
             raise ValueError("class_weights='balanced' is computed by the in-process runtime "
                              "(runtime.site) from every site's label counts; the COINSTAC phase "
                              "machines need the explicit list of class weights")
+        for c in (self.cfg, {**self.cfg, **(self.cfg.get("pretrain_args") or {})}):
+            # the phase machines neither know a phase's length in updates when the optimizer
+            # is built nor carry a plateau counter between rounds
+            if float(c.get("lr_plateau_factor") or 0) > 0:
+                raise ValueError("lr_plateau_factor is implemented by the in-process runtime "
+                                 "(runtime.site); the COINSTAC phase machines take warmup and "
+                                 "decay only")
+            if c.get("lr_schedule") in ("linear", "cosine") and c.get("lr_decay_steps") is None:
+                raise ValueError(f"lr_schedule={c.get('lr_schedule')!r} needs an explicit "
+                                 "lr_decay_steps in the COINSTAC phase machines")
         if not self._device_arg:
             from ..parallel.group import resolve_device
             self.device = resolve_device(self.cfg.get("gpus"))
@@ -173,10 +183,15 @@ class LocalNode:
                                verbose=False)
             logs = {}
             from ..parallel import DSGDEngine
+            plr = float(pa.get("learning_rate", self.trainer.optimizer.lr))
+            if lr_schedule_of(pcfg) is not None or lr_schedule_of(cfg) is not None:
+                # the phase's own schedule (on / off is fixed when the optimizer is built)
+                self.trainer._init_optimizer(lr=plr, cache=pcfg)
+            else:
+                self.trainer.optimizer.lr = plr
             eng = DSGDEngine(self.trainer.modules(), self.trainer.flat, SiteGroup(device=self.device),
                              pcfg, overlap=False)
             eng.name = "dSGD-local"
-            self.trainer.optimizer.lr = float(pa.get("learning_rate", self.trainer.optimizer.lr))
             fs._train_epochs(self.trainer, eng, self.data, pcfg, SiteGroup(device=self.device),
                              self.fold_dir, self.seed, logs, tag="pretrain_")
             self.trainer.load_checkpoint(os.path.join(self.fold_dir, "pretrain_checkpoint_best.pt"))

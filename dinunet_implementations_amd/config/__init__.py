@@ -76,6 +76,18 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     "dsgd_bucket_mb": 4.0,
     # global-norm gradient clipping in the fused Adam (ops.FusedAdam max_grad_norm): 0 = off
     "max_grad_norm": 0,
+    # learning-rate schedule in the fused Adam (ops.FusedAdam lr_schedule): None = off, or
+    # "constant" / "linear" / "cosine" decay to lr_min at update lr_decay_steps (None: epochs x
+    # updates per epoch of the phase that trains) after lr_warmup_steps updates of linear
+    # warmup; lr_plateau_factor in (0, 1) multiplies the rate after more than
+    # lr_plateau_patience validations in a row without improvement (0 = off).  The schedule is
+    # on when lr_schedule is set, lr_warmup_steps > 0 or lr_plateau_factor > 0
+    "lr_schedule": None,
+    "lr_warmup_steps": 0,
+    "lr_decay_steps": None,
+    "lr_min": 0.0,
+    "lr_plateau_factor": 0,
+    "lr_plateau_patience": 2,
     # loss options of the fused classifier heads (ops.head): F.cross_entropy's per-class weight
     # and label smoothing, every batch normalised by its own sum_i weight[y_i].  class_weights:
     # None, a list of num_class finite numbers > 0, or "balanced" (n_total / (C * n_c) from the
@@ -271,6 +283,60 @@ def build_config(*, site_input: Optional[Dict[str, Any]] = None,
     return validate(flat)
 
 
+LR_SCHEDULE_KINDS = ("constant", "linear", "cosine")
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _is_num(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def check_lr_schedule(cfg: Dict[str, Any]) -> None:
+    """The learning-rate schedule keys of ``cfg`` (normalised in place)."""
+    kind = cfg.get("lr_schedule") or None
+    if kind is not None and kind not in LR_SCHEDULE_KINDS:
+        raise ValueError(f"lr_schedule must be one of {LR_SCHEDULE_KINDS} or None, got {kind!r}")
+    cfg["lr_schedule"] = kind
+    W = cfg.get("lr_warmup_steps") or 0
+    if not _is_int(W) or W < 0:
+        raise ValueError(f"lr_warmup_steps must be an integer >= 0, got {W!r}")
+    cfg["lr_warmup_steps"] = W
+    T = cfg.get("lr_decay_steps")
+    if T is not None and (not _is_int(T) or T < 0):
+        raise ValueError(f"lr_decay_steps must be an integer >= 0 or None, got {T!r}")
+    if T is not None and kind in ("linear", "cosine") and T <= W:
+        raise ValueError(f"lr_decay_steps ({T}) must exceed lr_warmup_steps ({W})")
+    lo = cfg.get("lr_min") or 0.0
+    lr = cfg.get("learning_rate", 1e-3)
+    if not _is_num(lo) or not (0 <= lo <= (lr if _is_num(lr) else float("inf"))):
+        raise ValueError(f"lr_min must lie in [0, learning_rate = {lr!r}], got {lo!r}")
+    cfg["lr_min"] = lo
+    f = cfg.get("lr_plateau_factor") or 0
+    if not _is_num(f) or not (f == 0 or 0 < f < 1):
+        raise ValueError(f"lr_plateau_factor must be 0 (off) or lie in (0, 1), got {f!r}")
+    cfg["lr_plateau_factor"] = f
+    pp = cfg.get("lr_plateau_patience", 2)
+    pp = 2 if pp is None else pp
+    if not _is_int(pp) or pp < 0:
+        raise ValueError(f"lr_plateau_patience must be an integer >= 0, got {pp!r}")
+    cfg["lr_plateau_patience"] = pp
+
+
+def lr_schedule_of(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
+    """``FusedAdam``'s ``lr_schedule`` for ``cfg``: None when the schedule is off (``lr_schedule``
+    unset, no warmup, no plateau reduction)."""
+    kind = cfg.get("lr_schedule") or None
+    W = int(cfg.get("lr_warmup_steps") or 0)
+    if kind is None and W <= 0 and not (cfg.get("lr_plateau_factor") or 0) > 0:
+        return None
+    T = cfg.get("lr_decay_steps")
+    return {"kind": kind or "constant", "warmup_steps": W,
+            "decay_steps": None if T is None else int(T), "lr_min": float(cfg.get("lr_min") or 0.0)}
+
+
 def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     eng = cfg.get("agg_engine")
     if eng not in ("dSGD", "rankDAD", "powerSGD"):
@@ -288,6 +354,9 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if isinstance(mg, bool) or not isinstance(mg, (int, float)) or not (0 <= mg <= 3.4e38):
         raise ValueError(f"max_grad_norm must be a number >= 0 (0 = off), got {mg!r}")
     cfg["max_grad_norm"] = mg
+    check_lr_schedule(cfg)
+    if isinstance(cfg.get("pretrain_args"), dict):  # the pretraining phase may override each key
+        check_lr_schedule({**cfg, **cfg["pretrain_args"]})
     ls = cfg.get("label_smoothing", 0)
     ls = 0 if ls is None else ls
     if isinstance(ls, bool) or not isinstance(ls, (int, float)) or not (0 <= ls < 1):

@@ -58,21 +58,63 @@ __device__ __forceinline__ float clip_coef(ClipState* __restrict__ cs, float gra
   return (float)((double)grad_scale * fmin(1.0, (double)cs->max_norm / (G + 1e-6)));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Learning-rate schedule (FusedAdam lr_schedule).  The rate is a function of the update number t
+// the bias corrections use, evaluated in the prologue of every updating wave from a small device
+// block, so a captured graph follows the schedule -- and a host write to base / scale -- with no
+// recapture and no extra launch.
+enum LrKind { LR_CONSTANT = 0, LR_LINEAR = 1, LR_COSINE = 2 };
+struct LrState {
+  float base;       // host-written: the base rate (FusedAdam.lr)
+  float scale;      // host-written: the plateau multiplier (FusedAdam.lr_scale)
+  float lr_min;     // host-written: the rate the decay ends at
+  int kind;         // host-written: LrKind
+  int warmup;       // host-written: W, warmup length in updates
+  int decay_steps;  // host-written: T, total schedule length (<= W: no decay yet)
+  float applied;    // kernel-written: the rate the last update used
+  int pad;
+};
+
+//   w(t) = t < W ? t / W : 1
+//   u(t) = clamp((t - W) / (T - W), 0, 1)
+//   d(t) = 1 | 1 - (1 - r) u | r + (1 - r) 0.5 (1 + cos(pi u)),   r = lr_min / base
+//   lr(t) = (float)(((base * scale) * w) * d)
+// in double, rounded to fp32 once (FusedAdam.lr_at is the host mirror, same order of operations).
+// Constant, W = 0, scale = 1 gives base back exactly.  Workgroup 0 records the rate.
+__device__ __forceinline__ float sched_lr(LrState* __restrict__ ls, int t) {
+  const double base = (double)ls->base, td = (double)t;
+  const int W = ls->warmup, T = ls->decay_steps, kind = ls->kind;
+  const double w = t < W ? td / (double)W : 1.0;
+  double d = 1.0;
+  if (kind != LR_CONSTANT && T > W) {
+    const double u = fmin(fmax((td - (double)W) / (double)(T - W), 0.0), 1.0);
+    const double r = base > 0.0 ? (double)ls->lr_min / base : 1.0;
+    d = kind == LR_LINEAR ? 1.0 - (1.0 - r) * u
+                          : r + (1.0 - r) * 0.5 * (1.0 + cos(3.14159265358979323846 * u));
+  }
+  const float lr = (float)(((base * (double)ls->scale) * w) * d);
+  if (blockIdx.x == 0 && threadIdx.x == 0) ls->applied = lr;
+  return lr;
+}
+
 // torch.optim.Adam semantics (L2 weight decay, no amsgrad):
 //   g += wd * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
 // grad_scale folds the dSGD mean (1/world) or loss scaling into the same pass.
 // CLIP: the gradient scale and the skip flag come from clip_coef (cs non-null).
-template <bool CLIP>
+// SCHED: lr comes from sched_lr at this update's number (ls non-null; tdev null: tofs is the
+// host's step number); a skipped update still evaluates and records it.
+template <bool CLIP, bool SCHED>
 __global__ void __launch_bounds__(256)
 adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
             float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
             float bc1, float inv_sqrt_bc2, float grad_scale, const int* __restrict__ tdev,
             double b1d, double b2d, int tofs, long long* __restrict__ cursor,
-            ClipState* __restrict__ cs) {
+            ClipState* __restrict__ cs, LrState* __restrict__ ls) {
   // the device-fed batch cursor (prologue.h) advances once per update; no workgroup of this
   // launch reads it
   if (cursor && blockIdx.x == 0 && threadIdx.x == 0) *cursor += 1;
+  if constexpr (SCHED) lr = sched_lr(ls, tdev ? *tdev + tofs : tofs);
   if constexpr (CLIP) {
     bool skip;
     grad_scale = clip_coef(cs, grad_scale, skip);
@@ -254,13 +296,13 @@ __device__ __forceinline__ void record_step(const StepRecord& r, int cofs) {
 
 __global__ void __launch_bounds__(256) record_kernel(StepRecord r, int cofs) { record_step(r, cofs); }
 
-template <bool CLIP>
+template <bool CLIP, bool SCHED>
 __global__ void __launch_bounds__(256)
 adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                  float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
                  float grad_scale, const int* __restrict__ tdev, double b1d, double b2d, int update,
                  int zero_grad, PackPlan pl, StepPrologue sp, int gofs, int ublocks, StepRecord rec,
-                 ClipState* __restrict__ cs) {
+                 ClipState* __restrict__ cs, LrState* __restrict__ ls) {
   // the step's train record (rec.out set): the LAST workgroup; the cursor was advanced by this
   // step's encoder GEMM, so it names the batch this step trained on
   if (rec.out && blockIdx.x == gridDim.x - 1) {
@@ -276,6 +318,9 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
     for (long i = (blockIdx.x - ublocks) * (long)blockDim.x + threadIdx.x; i < ng; i += stride)
       prologue_item(sp, i, c);  // sp.ug == 0: the zeroing rides in the update below
     return;
+  }
+  if constexpr (SCHED) {  // (priming launches, update = 0, leave the recorded rate alone)
+    if (update) lr = sched_lr(ls, *tdev);
   }
   if constexpr (CLIP) {  // (launched with update set only)
     bool skip;
@@ -373,16 +418,26 @@ DN_API int dn_grad_sqnorm(const float* g, long n, void* clip, hipStream_t st) {
   return dn_launch_status();
 }
 
+DN_API long dn_lr_state_size() { return (long)sizeof(LrState); }
+
+// the <CLIP, SCHED> instantiation for a launch's clip / sched pointers (null = off)
+#define DN_ADAM_PICK(KERNEL, clip, sched)                        \
+  ((clip) ? ((sched) ? KERNEL<true, true> : KERNEL<true, false>) \
+          : ((sched) ? KERNEL<false, true> : KERNEL<false, false>))
+
 // clip (a ClipState dn_grad_sqnorm filled for this gradient) non-null: the clipped update.
+// sched (an LrState) non-null: the scheduled rate at update number `step` (the host's count)
+// replaces lr.
 DN_API int dn_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1,
                    float b2, float eps, float wd, float bc1, float inv_sqrt_bc2, float grad_scale,
-                   long long* cursor, void* clip, hipStream_t st) {
+                   long long* cursor, void* clip, int step, void* sched, hipStream_t st) {
   if (n <= 0) return DN_OK;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(clip ? adam_kernel<true> : adam_kernel<false>, dim3(grid_for(n / 4 + 1)),
+  if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
+  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched), dim3(grid_for(n / 4 + 1)),
                      dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, inv_sqrt_bc2,
-                     grad_scale, (const int*)nullptr, 0.0, 0.0, 1, cursor,
-                     reinterpret_cast<ClipState*>(clip));
+                     grad_scale, (const int*)nullptr, 0.0, 0.0, sched ? step : 1, cursor,
+                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched));
   return dn_launch_status();
 }
 
@@ -390,13 +445,14 @@ DN_API int dn_adam(float* p, const float* g, float* m, float* v, long n, float l
 // HIP graph and replayed every step with the right bias corrections.  *tdev = completed steps.
 DN_API int dn_adam_dev(float* p, const float* g, float* m, float* v, long n, float lr, double b1,
                        double b2, float eps, float wd, float grad_scale, int* tdev, int prebumped,
-                       long long* cursor, void* clip, hipStream_t st) {
+                       long long* cursor, void* clip, void* sched, hipStream_t st) {
   if (n <= 0) return DN_OK;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(clip ? adam_kernel<true> : adam_kernel<false>, dim3(grid_for(n / 4 + 1)),
+  if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
+  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched), dim3(grid_for(n / 4 + 1)),
                      dim3(256), 0, st, p, g, m, v, n, lr, (float)b1, (float)b2, eps, wd, 0.f, 0.f,
                      grad_scale, (const int*)tdev, b1, b2, prebumped ? 0 : 1, cursor,
-                     reinterpret_cast<ClipState*>(clip));
+                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched));
   if (!prebumped) hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, tdev);
   return dn_launch_status();
 }
@@ -410,9 +466,10 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
                         int HD, const void* gx, int gx_bf16, long row_elems, const long long* gy,
                         const long long* order, long nb, const long long* cursor, int B,
                         void* xb, long long* yd, long long* sd, int gofs, const void* record,
-                        void* clip, hipStream_t st) {
+                        void* clip, void* sched, hipStream_t st) {
   if (n <= 0 || n % 4 || cnt < 0 || cnt > PACK_SEGS) return DN_BAD_SHAPE;
   if (clip && !update) return DN_BAD_SHAPE;  // the partials belong to an update's gradient
+  if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
   StepRecord rec{};
   if (record && update) {
     rec = *reinterpret_cast<const StepRecord*>(record);
@@ -447,10 +504,11 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
   // rest start as the first retire)
   auto parts = [](long items) { return (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096); };
   const int ub = parts(n / 4), gb = sp.gx ? parts(sp.ux + sp.ny) : 0;
-  hipLaunchKernelGGL(clip ? adam_pack_kernel<true> : adam_pack_kernel<false>,
+  hipLaunchKernelGGL(DN_ADAM_PICK(adam_pack_kernel, clip, sched),
                      dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, p, g, m, v, n, lr,
                      (float)b1, (float)b2, eps, wd, grad_scale, tdev, b1, b2, update, zero_grad, pl,
-                     sp, gofs, ub, rec, reinterpret_cast<ClipState*>(clip));
+                     sp, gofs, ub, rec, reinterpret_cast<ClipState*>(clip),
+                     reinterpret_cast<LrState*>(sched));
   return dn_launch_status();
 }
 

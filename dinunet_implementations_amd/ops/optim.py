@@ -13,7 +13,9 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Dict, Iterable, List, Optional
+import struct
+from dataclasses import asdict, dataclass
+from typing import Dict, Iterable, List, Optional, Union
 
 import torch
 import torch.nn as nn
@@ -21,11 +23,13 @@ import torch.nn as nn
 from . import _lib
 
 _lib.register("dn_adam", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
-                          _lib.c_long] + [_lib.c_float] * 8 + [_lib.c_void_p] * 3)
+                          _lib.c_long] + [_lib.c_float] * 8 + [_lib.c_void_p] * 2
+              + [_lib.c_int] + [_lib.c_void_p] * 2)
 _lib.register("dn_adam_dev", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
                               _lib.c_long, _lib.c_float, _lib.c_double, _lib.c_double,
                               _lib.c_float, _lib.c_float, _lib.c_float, _lib.c_void_p,
-                              _lib.c_int, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p])
+                              _lib.c_int, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
+                              _lib.c_void_p])
 _lib.register("dn_grad_sqnorm", [_lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_void_p])
 _lib.register("dn_step_gather", [_lib.c_void_p, _lib.c_int, _lib.c_long, _lib.c_void_p,
                                  _lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_int,
@@ -49,7 +53,7 @@ _lib.register("dn_adam_pack", [_lib.c_void_p] * 4 + [_lib.c_long, _lib.c_float, 
                                _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
                                _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
                                _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
-                               _lib.c_void_p])
+                               _lib.c_void_p, _lib.c_void_p])
 _lib.register("dn_step_record", [_lib.c_void_p, _lib.c_int, _lib.c_void_p])
 
 
@@ -126,6 +130,64 @@ def clip_coef(grad: torch.Tensor, grad_scale: float, max_norm: float):
     return float(torch.tensor(coef, dtype=torch.float32)), G
 
 
+# optim.hip LrState: 8 four-byte words {fp32 base, fp32 scale, fp32 lr_min, int32 kind, int32
+# warmup, int32 decay_steps, fp32 applied, pad} (size checked against the library on a GPU)
+LR_KINDS = {"constant": 0, "linear": 1, "cosine": 2}
+_LR_BASE, _LR_SCALE, _LR_MIN, _LR_KIND, _LR_WARMUP, _LR_DECAY, _LR_APPLIED = range(7)
+LR_WORDS = 8
+
+
+def _f32(x: float) -> float:
+    """``x`` rounded to fp32 (what a device word holds), as a Python double."""
+    return struct.unpack("f", struct.pack("f", float(x)))[0]
+
+
+@dataclass
+class LrSchedule:
+    """A learning rate as a function of the update number ``t`` (:meth:`FusedAdam.lr_at`):
+    ``warmup_steps`` updates of linear warmup, then ``kind`` (``constant`` / ``linear`` /
+    ``cosine``) decay to ``lr_min`` at update ``decay_steps``.  ``decay_steps=None``: not known
+    yet (no decay until :meth:`FusedAdam.set_decay_steps`)."""
+    kind: str = "constant"
+    warmup_steps: int = 0
+    decay_steps: Optional[int] = None
+    lr_min: float = 0.0
+
+    @staticmethod
+    def of(spec: Union["LrSchedule", Dict, str]) -> "LrSchedule":
+        if isinstance(spec, LrSchedule):
+            return LrSchedule(**asdict(spec))
+        if isinstance(spec, str):
+            return LrSchedule(kind=spec)
+        if isinstance(spec, dict):
+            unknown = set(spec) - {"kind", "warmup_steps", "decay_steps", "lr_min"}
+            if unknown:
+                raise ValueError(f"lr_schedule: unknown entries {sorted(unknown)}")
+            return LrSchedule(**spec)
+        raise ValueError(f"lr_schedule must be an LrSchedule, a dict or a kind name, got {spec!r}")
+
+    def check(self, lr: float) -> "LrSchedule":
+        if self.kind not in LR_KINDS:
+            raise ValueError(f"lr_schedule kind must be one of {sorted(LR_KINDS)}, got {self.kind!r}")
+        for name in ("warmup_steps", "decay_steps"):
+            v = getattr(self, name)
+            if v is None and name == "decay_steps":
+                continue
+            if isinstance(v, bool) or not isinstance(v, int) or not (0 <= v < 2 ** 31):
+                raise ValueError(f"lr_schedule {name} must be an integer >= 0, got {v!r}")
+        if isinstance(self.lr_min, bool) or not (0.0 <= float(self.lr_min) <= float(lr)):
+            raise ValueError(f"lr_schedule lr_min must lie in [0, lr = {lr!r}], got {self.lr_min!r}")
+        if (self.kind != "constant" and self.decay_steps is not None
+                and self.decay_steps <= self.warmup_steps):
+            raise ValueError(f"lr_schedule decay_steps ({self.decay_steps}) must exceed "
+                             f"warmup_steps ({self.warmup_steps}) for a {self.kind} decay")
+        return self
+
+
+def _capturing() -> bool:
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
 class FusedAdam:
     """``torch.optim.Adam`` on a :class:`FlatParams` buffer in one kernel launch per step.
 
@@ -138,12 +200,26 @@ class FusedAdam:
     batch gathered, cursor and step number advanced) still happens.  ``None``: the
     ``DINUNET_MAX_GRAD_NORM`` switch, else off; ``0``: off.  On / off is fixed here (it changes
     what is launched); the threshold itself lives on the device and may change between replays of
-    a captured graph."""
+    a captured graph.
+
+    ``lr_schedule`` (an :class:`LrSchedule`, a dict of its fields or a kind name): the rate of
+    update ``t`` is :meth:`lr_at` -- warmup, decay and the plateau multiplier ``lr_scale`` --
+    evaluated on the device in the prologue of the Adam launch from the same update number as the
+    bias corrections, the same on every step form; ``applied_lr`` holds the rate the last update
+    used.  An update skipped by the clipping still consumes its number, so the schedule advances.
+    ``None``: the ``DINUNET_LR_SCHEDULE`` switch (``constant|linear|cosine``; the decaying kinds
+    run to ``DINUNET_LR_DECAY_STEPS``, default 10000), else off.  On / off is fixed here (it
+    changes what is launched); ``lr``, ``lr_scale`` and the schedule's numbers live on the device,
+    so they may change between replays of a captured graph.  ``constant`` with no warmup and
+    ``lr_scale`` 1 is bit-identical to the schedule being off."""
 
     def __init__(self, flat: FlatParams, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, max_grad_norm: Optional[float] = None):
+                 weight_decay: float = 0.0, max_grad_norm: Optional[float] = None,
+                 lr_schedule: Union[LrSchedule, Dict, str, None] = None):
         self.flat = flat
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self._lrs: Optional[torch.Tensor] = None  # schedule state (optim.hip LrState)
+        self._lr = float(lr)
+        self.betas, self.eps, self.weight_decay = betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
         self.step_count = 0
@@ -170,6 +246,139 @@ class FusedAdam:
             self._clip_f = self._clip[CLIP_PARTS:].view(torch.float32)
             self._clip_i = self._clip[CLIP_PARTS:].view(torch.int32)
             self._clip_f[0] = c
+        if lr_schedule is None:
+            env = os.environ.get("DINUNET_LR_SCHEDULE", "")
+            if env:
+                lr_schedule = LrSchedule(kind=env)
+                if env != "constant":
+                    lr_schedule.decay_steps = int(os.environ.get("DINUNET_LR_DECAY_STEPS", "")
+                                                  or 10000)
+        self._sched: Optional[LrSchedule] = None
+        self._lr_scale = 1.0
+        self.plateau_wait = 0  # validations without improvement (plateau_step)
+        if lr_schedule is not None:
+            self._sched = LrSchedule.of(lr_schedule).check(self._lr)
+            dev = flat.data.device
+            if dev.type == "cuda":
+                L = _lib.lib()
+                L.dn_lr_state_size.restype = _lib.c_long
+                if int(L.dn_lr_state_size()) != LR_WORDS * 4:
+                    raise RuntimeError("lr state layout mismatch with the kernel library")
+            self._lrs = torch.zeros(LR_WORDS, dtype=torch.int32, device=dev)
+            self._lrs_f = self._lrs.view(torch.float32)
+            self._write_lr_state()
+
+    # learning-rate schedule ---------------------------------------------------------------------
+    def _write_lr_state(self):
+        """All host-written words of the device block from the host values (one small copy)."""
+        sc = self._sched
+        w = struct.pack("fffiii", self._lr, self._lr_scale, sc.lr_min, LR_KINDS[sc.kind],
+                        sc.warmup_steps, sc.decay_steps or 0)
+        self._lrs[:_LR_APPLIED].copy_(torch.tensor(struct.unpack("6i", w), dtype=torch.int32))
+
+    def _refuse_in_capture(self, what: str):
+        if self._lrs is not None and _capturing():
+            # the write would become a graph node that resets the value at every replay
+            raise RuntimeError(f"FusedAdam.{what} set inside a HIP graph capture")
+
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    @lr.setter
+    def lr(self, value: float):
+        value = float(value)
+        if self._lrs is None:
+            self._lr = value
+            return
+        self._refuse_in_capture("lr")
+        if not (self._sched.lr_min <= value):
+            raise ValueError(f"FusedAdam.lr {value!r} is below the schedule's lr_min "
+                             f"{self._sched.lr_min!r}")
+        self._lr = value
+        self._write_lr_state()
+
+    @property
+    def lr_schedule(self) -> Optional[LrSchedule]:
+        """The schedule as built (a copy), None with the schedule off."""
+        return None if self._sched is None else LrSchedule.of(self._sched)
+
+    def _need_schedule(self, what: str):
+        if self._lrs is None:
+            raise ValueError(f"FusedAdam.{what}: the schedule is switched on or off when the "
+                             "optimizer is built (it changes what is launched)")
+
+    @property
+    def lr_scale(self) -> float:
+        """The plateau multiplier on the scheduled rate (1 with the schedule off)."""
+        return self._lr_scale
+
+    @lr_scale.setter
+    def lr_scale(self, value: float):
+        self._need_schedule("lr_scale")
+        value = float(value)
+        if not (0.0 < value <= 3.4e38):
+            raise ValueError(f"FusedAdam.lr_scale must be a finite number > 0, got {value!r}")
+        self._refuse_in_capture("lr_scale")
+        self._lr_scale = value
+        self._write_lr_state()
+
+    def set_decay_steps(self, steps: int):
+        """The update number at which the decay reaches ``lr_min``."""
+        self._need_schedule("set_decay_steps")
+        sc = LrSchedule.of(self._sched)
+        sc.decay_steps = steps if steps is None else int(steps)
+        sc.check(self._lr)
+        self._refuse_in_capture("decay_steps")
+        self._sched = sc
+        self._write_lr_state()
+
+    @property
+    def applied_lr(self) -> Optional[torch.Tensor]:
+        """fp32 [] on the optimizer's device: the rate the last update used (None with the
+        schedule off)."""
+        return None if self._lrs is None else self._lrs_f[_LR_APPLIED]
+
+    def lr_at(self, t: int) -> float:
+        """The rate of update number ``t`` (1-based) as the kernels compute it (optim.hip
+        sched_lr): from the fp32 device words, in double, rounded to fp32 once::
+
+            w = t / W if t < W else 1
+            u = clamp((t - W) / (T - W), 0, 1)
+            d = 1 | 1 - (1 - r) u | r + (1 - r) 0.5 (1 + cos(pi u)),  r = lr_min / base
+            lr = fp32(((base * scale) * w) * d)
+
+        With the schedule off this is ``lr``."""
+        if self._sched is None:
+            return self._lr
+        sc = self._sched
+        base, scale, t = _f32(self._lr), _f32(self._lr_scale), int(t)
+        W, T = sc.warmup_steps, sc.decay_steps or 0
+        w = t / W if t < W else 1.0
+        d = 1.0
+        if sc.kind != "constant" and T > W:
+            u = min(max((t - W) / (T - W), 0.0), 1.0)
+            r = _f32(sc.lr_min) / base if base > 0.0 else 1.0
+            d = (1.0 - (1.0 - r) * u if sc.kind == "linear"
+                 else r + (1.0 - r) * 0.5 * (1.0 + math.cos(math.pi * u)))
+        return _f32(((base * scale) * w) * d)
+
+    def plateau_step(self, improved: bool, factor: float, patience: int) -> bool:
+        """Reduce-on-plateau bookkeeping for one validation result: an improvement resets the
+        counter, anything else advances it, and once it exceeds ``patience`` the multiplier
+        becomes ``max(lr_scale * factor, lr_min / lr)`` and the counter restarts.  True when
+        this call reduced (or tried to: at the floor the multiplier stays)."""
+        self._need_schedule("plateau_step")
+        if improved:
+            self.plateau_wait = 0
+            return False
+        self.plateau_wait += 1
+        if self.plateau_wait <= int(patience):
+            return False
+        self.plateau_wait = 0
+        floor = self._sched.lr_min / self._lr if self._lr > 0 else 0.0
+        self.lr_scale = max(self._lr_scale * float(factor), floor)
+        return True
 
     # global-norm clipping ----------------------------------------------------------------------
     @property
@@ -222,8 +431,12 @@ class FusedAdam:
             _lib.call("dn_adam", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
                       self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
                       self.weight_decay, bc1, 1.0 / math.sqrt(bc2), grad_scale,
-                      _lib.ptr(self.cursor), clip, _lib.stream())
+                      _lib.ptr(self.cursor), clip, self.step_count, _lib.ptr(self._lrs),
+                      _lib.stream())
             return
+        lr = self.lr_at(self.step_count)
+        if self._lrs is not None:  # (recorded for a skipped update too: it consumed its number)
+            self._lrs_f[_LR_APPLIED] = lr
         if self._clip is not None:
             grad_scale, G = clip_coef(self.flat.grad, grad_scale, self._max_grad_norm)
             self._clip_f[1] = G
@@ -236,7 +449,7 @@ class FusedAdam:
         self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
         self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
         denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(self.eps)
-        d.addcdiv_(self.exp_avg, denom, value=-self.lr / bc1)
+        d.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
 
     # HIP-graph form --------------------------------------------------------------------------
     def sync_device_step(self):
@@ -264,7 +477,7 @@ class FusedAdam:
         _lib.call("dn_adam_dev", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
                   self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
                   self.weight_decay, grad_scale, self._tdev.data_ptr(), int(prebumped),
-                  _lib.ptr(self.cursor), clip, _lib.stream())
+                  _lib.ptr(self.cursor), clip, _lib.ptr(self._lrs), _lib.stream())
 
     # Adam that also emits the next step's operands (optim.hip adam_pack_kernel) ------------------
     def attach_pack(self, pack, src=None, xb: Optional[torch.Tensor] = None,
@@ -316,7 +529,7 @@ class FusedAdam:
                   self.weight_decay, grad_scale, self._tdev.data_ptr(), int(update), 1,
                   ctypes_addr(tab), cnt, pack.I, pack.Hd, pack.HD, *gx, int(gofs),
                   ctypes_addr(record) if (record is not None and update) else None, clip,
-                  _lib.stream())
+                  _lib.ptr(self._lrs), _lib.stream())
 
     def device_step(self) -> torch.Tensor:
         """The device step counter (int32[1]) the graph-captured update reads; a step prologue
@@ -332,9 +545,19 @@ class FusedAdam:
         if self._clip is not None:
             sd["max_grad_norm"] = self._max_grad_norm
             sd["skipped"] = int(self.skipped_steps.item())
+        if self._sched is not None:
+            sd["lr_schedule"] = asdict(self._sched)
+            sd["lr_scale"] = self._lr_scale
+            sd["plateau_wait"] = int(self.plateau_wait)
         return sd
 
     def load_state_dict(self, sd: Dict):
+        if self._sched is not None:  # (on / off stays as built; older checkpoints carry none)
+            if sd.get("lr_schedule"):
+                self._sched = LrSchedule.of(dict(sd["lr_schedule"])).check(
+                    float(sd.get("lr", self._lr)))
+            self._lr_scale = float(sd.get("lr_scale", self._lr_scale))
+            self.plateau_wait = int(sd.get("plateau_wait", self.plateau_wait))
         self.lr = sd.get("lr", self.lr)
         self.betas = tuple(sd.get("betas", self.betas))
         self.eps = sd.get("eps", self.eps)

@@ -31,7 +31,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from ..config import site_seed
+from ..config import lr_schedule_of, site_seed
 from ..data.loader import DeviceLoader
 from ..data.splits import make_splits
 from ..parallel import SiteGroup, make_engine
@@ -330,6 +330,12 @@ class FederatedSite:
                 step = TrainStep(trainer.modules(), trainer.flat, trainer.optimizer, engine,
                                  use_graph=use_graph, accum=li,
                                  forward_loss=lambda m, x, y: trainer.forward_loss(x, y))
+        opt = trainer.optimizer
+        sched_on = getattr(opt, "applied_lr", None) is not None
+        plateau = float(cfg.get("lr_plateau_factor") or 0) if sched_on else 0.0
+        if sched_on and not resume and cfg.get("lr_decay_steps") is None:
+            # a fresh phase: the decay ends with its last update (a resumed one carries its own)
+            opt.set_decay_steps(max(epochs * steps, opt.lr_schedule.warmup_steps + 1))
         fault_at = _fault_step(self.group.rank)
         feed = self._device_feed(trainer, step, engine, tr, bs, li, steps, cfg, fault_at)
         if resume and resume.get("loader"):
@@ -413,6 +419,8 @@ class FederatedSite:
                 logs.setdefault(f"{tag}grad_norm", []).append(float(trainer.optimizer.grad_norm))
                 logs.setdefault(f"{tag}skipped_steps", []).append(
                     int(trainer.optimizer.skipped_steps))
+            if sched_on:  # the rate the epoch's last update used
+                logs.setdefault(f"{tag}learning_rate", []).append(float(opt.applied_lr))
             tl.append([round(avg.average, 6)] + met.get((monitor if monitor != "loss" else "auc",)))
             logs.setdefault(f"{tag}samples_per_sec", []).append(nsamp / dt if dt > 0 else 0.0)
             stop = False
@@ -428,7 +436,12 @@ class FederatedSite:
                 lvl.append([round(r["local_loss"], 6),
                             round(r["local_loss"] if monitor.lower() == "loss"
                                   else metric_value(r["local_scores"], monitor), 6)])
-                if improved(score, best["score"], direction):
+                better = improved(score, best["score"], direction)
+                if plateau > 0 and opt.plateau_step(better, plateau,
+                                                    int(cfg.get("lr_plateau_patience", 2))):
+                    # every rank sees the same global score, so every rank reduces alike
+                    logs.setdefault(f"{tag}lr_reduced_epochs", []).append(epoch)
+                if better:
                     best.update(score=score, epoch=epoch, wait=0)
                     trainer.save_checkpoint(os.path.join(fold_dir, f"{tag}checkpoint_best.pt"),
                                             epoch=epoch, best_val_epoch=epoch, best_val_score=score)
@@ -516,7 +529,13 @@ class FederatedSite:
                 from ..parallel import DSGDEngine
                 from ..parallel.group import SiteGroup as _SG
                 solo = _SG(device=self.device)
-                trainer.optimizer.lr = float(pa.get("learning_rate", trainer.optimizer.lr))
+                if lr_schedule_of(pcfg) is not None or lr_schedule_of(self.cfg) is not None:
+                    # the phase's own schedule (pretrain_args may override each key; on / off
+                    # is fixed when the optimizer is built): nothing is trained yet
+                    trainer._init_optimizer(
+                        lr=float(pa.get("learning_rate", trainer.optimizer.lr)), cache=pcfg)
+                else:
+                    trainer.optimizer.lr = float(pa.get("learning_rate", trainer.optimizer.lr))
                 eng = DSGDEngine(trainer.modules(), trainer.flat, solo, pcfg, overlap=False)
                 eng.name = "dSGD-local"
                 self.log(f"pretraining alone on {sizes[src]} samples for {pa.get('epochs')} epochs")

@@ -374,8 +374,11 @@ class TrainStep:
         self.calls += 1
         if not self.use_graph:
             return self._eager(x, y, first, last)
-        if self.graph is not None and self.graph_opt and self.opt.lr != self._cap_lr:
-            self.graph = None  # the learning rate is baked into the captured update
+        if (self.graph is not None and self.graph_opt and self.opt.lr != self._cap_lr
+                and getattr(self.opt, "applied_lr", None) is None):
+            # the learning rate is baked into the captured update (a scheduled optimizer
+            # holds it on the device: its graphs follow the change)
+            self.graph = None
         if self.graph is None:
             if self.calls <= self.eager_warmup * self.accum:
                 s = torch.cuda.Stream()
@@ -732,9 +735,12 @@ class TrainStep:
             else:
                 loss = self._dev_eager()
             return loss, done + 1, primed
-        if self._dgraphs and self.opt.lr != self._cap_lr and any(
-                v[2] is True for v in self._dgraphs.values()):
-            self._dgraphs = {}  # the learning rate is baked into the captured update
+        if (self._dgraphs and self.opt.lr != self._cap_lr
+                and getattr(self.opt, "applied_lr", None) is None
+                and any(v[2] is True for v in self._dgraphs.values())):
+            # the learning rate is baked into the captured update (a scheduled optimizer
+            # holds it on the device: its graphs follow the change)
+            self._dgraphs = {}
         if self.split and not self.comm_graph and self.accum == 1:
             if "split" not in self._dgraphs:
                 self._dev_capture_split()

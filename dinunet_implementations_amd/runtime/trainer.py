@@ -21,6 +21,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ..config import lr_schedule_of
 from ..ops import FlatParams, FusedAdam
 from ..utils.metrics import Averages, Metrics
 
@@ -143,12 +144,16 @@ class NNTrainer:
         for k in sorted(self.nn):
             yield from self.nn[k].parameters()
 
-    def _init_optimizer(self, lr: Optional[float] = None):
+    def _init_optimizer(self, lr: Optional[float] = None, cache: Optional[Dict[str, Any]] = None):
+        """``cache``: the phase's configuration where it differs from the run's (pretraining)."""
+        cache = self.cache if cache is None else cache
         self.flat = FlatParams(self.parameters(), device=self.device["gpu"])
-        lr = float(lr if lr is not None else self.cache.get("learning_rate", 1e-3))
-        # (0 = off -> None, so the DINUNET_MAX_GRAD_NORM switch still applies)
-        self.optimizer = FusedAdam(self.flat, lr=lr, weight_decay=float(self.cache.get("weight_decay", 0.0)),
-                                   max_grad_norm=float(self.cache.get("max_grad_norm") or 0) or None)
+        lr = float(lr if lr is not None else cache.get("learning_rate", 1e-3))
+        # (0 = off -> None, so the DINUNET_MAX_GRAD_NORM switch still applies; likewise an
+        # unset schedule and DINUNET_LR_SCHEDULE)
+        self.optimizer = FusedAdam(self.flat, lr=lr, weight_decay=float(cache.get("weight_decay", 0.0)),
+                                   max_grad_norm=float(cache.get("max_grad_norm") or 0) or None,
+                                   lr_schedule=lr_schedule_of(cache))
 
     def modules(self) -> nn.Module:
         """All registered modules as one container (engines walk ``.modules()``)."""

@@ -1010,7 +1010,7 @@ lr_persist_kernel(LpArgs a) {
     LP_STAMP(sb);
     lp_stage(stg, rQ, (m * r + 3) & ~3, tid);
     lp_sync();
-    const int ncol = min(m, 16 * cb1) - 16 * cb0;
+    const int ncol = max(0, min(m, 16 * cb1) - 16 * cb0);  // none past the last column block
     for (int e = tid; e < ncol * r; e += 256) qold[e] = stg[16 * cb0 * r + e];  // my Q rows now
     {
 #if LP_BF16X3
@@ -1048,7 +1048,9 @@ lr_persist_kernel(LpArgs a) {
     }
     lp_sync();
     LP_STAMP(sb + 1);
-    const int nr = min(n, 16 * rb1) - 16 * rb0;  // my rows
+    // my rows; a member past the last row block has none (rb0 = rb1 = nrb, where 16 nrb may
+    // exceed n: unclamped, lp_publish's 4-byte tail then stored over P's last entries)
+    const int nr = max(0, min(n, 16 * rb1) - 16 * rb0);
     for (int e = tid; e < (rb1 - rb0) * 256; e += 256) {
       const int rb = e >> 8, i = (e >> 4) & 15, c2 = e & 15;
       const int rr = 16 * rb + i;
@@ -1247,7 +1249,7 @@ lr_persist_kernel(LpArgs a) {
     }
     if (stop) {
       // Psend for my rows from the last iteration's P (still staged) and factor, once per launch
-      const int nr = min(n, 16 * rb1) - 16 * rb0;
+      const int nr = max(0, min(n, 16 * rb1) - 16 * rb0);
       if (tid < nr) {
         float x[LR_MAXR];
         const int row = 16 * rb0 + tid;
@@ -1416,7 +1418,7 @@ DN_API int dn_lr_persist(const void* host_layers, int nl, int iters, float tol, 
   a.tol = tol;
   a.sync = sync;
   a.stamps = g_lp_stamps;
-  int jmax = 1;
+  int jmax = 1, live = 0;
   const LrLayer* hl = reinterpret_cast<const LrLayer*>(host_layers);
   for (int l = 0; l < nl; ++l) {
     LpLayer& Y = a.L[l];
@@ -1426,10 +1428,13 @@ DN_API int dn_lr_persist(const void* host_layers, int nl, int iters, float tol, 
     Y.gram = gram + (long)l * LP_MAXJ * 256;
     Y.norms = norms + (long)l * LP_MAXJ * 2;
     jmax = Y.J > jmax ? Y.J : jmax;
+    live += Y.J;
   }
   a.spin = dn_spin_limit(LP_SPIN);
-  // members of a layer meet at barriers: every workgroup must be resident at once (else the
-  // staged kernels, DN_UNSUPPORTED)
+  // members of a layer meet at barriers: every member workgroup must be resident at once (else
+  // the staged kernels, DN_UNSUPPORTED).  The grid also holds LP_MAXL * jmax - live workgroups
+  // without a layer or past their layer's J: they return at entry and wait for nobody, so they
+  // need no place of their own (counting them refused every J > 24 on 256 CUs)
   int rmax = 1, rmin = 1 << 30;
   for (int l = 0; l < nl; ++l) {
     rmax = a.L[l].X.r > rmax ? a.L[l].X.r : rmax;
@@ -1444,7 +1449,7 @@ DN_API int dn_lr_persist(const void* host_layers, int nl, int iters, float tol, 
   LP_PICK(4) LP_PICK(8) LP_PICK(10) LP_PICK(12) LP_PICK(16)
 #undef LP_PICK
   kfn = reinterpret_cast<const void*>(kl);
-  if (!dn_fits_resident(kfn, LP_MAXL * jmax, 256, 0))
+  if (!dn_fits_resident(kfn, live, 256, 0))
     return DN_UNSUPPORTED;
   hipLaunchKernelGGL(kl, dim3(LP_MAXL * jmax), dim3(256), 0, st, a);
   return dn_launch_status();

@@ -22,7 +22,6 @@ all-reduce SUM in place and folds ``1/world`` into the fused Adam launch).
 from __future__ import annotations
 
 import contextlib
-import ctypes
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -38,7 +37,7 @@ from .collective import (PAYLOAD_TYPES, SB, DirectMean, from_payload, launch_on,
                          payload_numel, to_payload)
 from .group import SiteGroup
 from .lowrank import EPS as EPS_MGS
-from .lowrank import LowRankTable, _mgs_torch_, dad_factors, orthonormalize_
+from .lowrank import LowRankTable, PiReconTable, _mgs_torch_, dad_factors, orthonormalize_
 
 Tensor = torch.Tensor
 
@@ -627,7 +626,6 @@ class RankDADEngine(Engine):
         """Device tables of the factorisation kernels (csrc/kernels/lowrank.hip): per large
         Linear, its gradient view, the warm-start / candidate Q, and the P and Q slots of the
         send buffer that the factor all-gather ships."""
-        import ctypes
         segs = {id(p): o for p, o, _ in self.flat.segments()}
         dev = self.flat.data.device
         gen = torch.Generator(device="cpu").manual_seed(int(self.cfg.get("seed", 0)) + 777)
@@ -687,25 +685,10 @@ class RankDADEngine(Engine):
                 self._peer_mean(("dense",), sum(b - a for a, b in self._dense_ranges))
             _peer.gather(self.group, dev, self._send.numel(), self.wire, ("rankDAD", "factors"))
 
-        class PiRecon(ctypes.Structure):
-            _fields_ = [("G", ctypes.c_void_p), ("P", ctypes.c_void_p), ("Q", ctypes.c_void_p),
-                        ("out", ctypes.c_int), ("inn", ctypes.c_int), ("r", ctypes.c_int),
-                        ("start", ctypes.c_long)]
-        L = _lib.lib()
-        L.dn_pi_recon_size.restype = ctypes.c_long
-        if ctypes.sizeof(PiRecon) != L.dn_pi_recon_size():
-            raise RuntimeError("reconstruction table layout mismatch with the kernel library")
-        rec = (PiRecon * n)()
-        start = 0
         G0, gat0 = self.flat.grad.data_ptr(), self._gathered.data_ptr()
-        for i, (_, o, out_f, in_f, rr, po, qo) in enumerate(self.fast_layers):
-            c = rec[i]
-            c.G, c.P, c.Q = G0 + 4 * o, gat0 + 4 * po, gat0 + 4 * qo
-            c.out, c.inn, c.r, c.start = out_f, in_f, rr, start
-            start += out_f * in_f
-        self._recon_total = start
-        self._rec_host = rec  # (the launcher reads the tile prefix from the host copy)
-        self._rec = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8).to(dev)
+        self._recon = PiReconTable(
+            [(G0 + 4 * o, gat0 + 4 * po, gat0 + 4 * qo, out_f, in_f, rr)
+             for _, o, out_f, in_f, rr, po, qo in self.fast_layers], dev)
 
     def state_dict(self):
         if self.fast and getattr(self, "fast_layers", None):
@@ -798,9 +781,7 @@ class RankDADEngine(Engine):
                 g.all_gather_into(self._gathered, self._send)
                 self.comm_bytes += self._send.numel() * 4
         # every layer's G = [P_1..P_W][Q_1..Q_W]^T / W in one launch
-        _lib.call("dn_pi_reconstruct", self._rec.data_ptr(), ctypes.addressof(self._rec_host),
-                  len(self.fast_layers),
-                  self._recon_total, self._send.numel(), W if g.distributed else 1, _lib.stream())
+        self._recon.run(self._send.numel(), W if g.distributed else 1)
         return 1.0
 
     def step_context(self):

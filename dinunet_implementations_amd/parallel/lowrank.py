@@ -205,3 +205,40 @@ class LowRankTable:
         if self.n:
             _lib.call("dn_lr_recon_ef", self.table.data_ptr(), self.host_table(), self.n,
                       _lib.stream())
+
+
+class PiReconTable:
+    """Layer records of ``dn_pi_reconstruct`` (rank-dAD: ``G_l = sum_s P_s Q_s^T / W`` for every
+    factorised layer, one launch).
+
+    ``records``: ``[(G address, P address, Q address, out, in, r)]``: ``G`` the ``[out, in]`` fp32
+    output, ``P`` / ``Q`` the layer's ``[out, r]`` / ``[in, r]`` factors of site 0 inside the
+    gathered send buffers (site ``s`` lies ``s * stride`` floats further, see :meth:`run`)."""
+
+    def __init__(self, records, device):
+        import ctypes
+
+        class PiRecon(ctypes.Structure):
+            _fields_ = [("G", ctypes.c_void_p), ("P", ctypes.c_void_p), ("Q", ctypes.c_void_p),
+                        ("out", ctypes.c_int), ("inn", ctypes.c_int), ("r", ctypes.c_int),
+                        ("start", ctypes.c_long)]
+        L = _lib.lib()
+        L.dn_pi_recon_size.restype = ctypes.c_long
+        if ctypes.sizeof(PiRecon) != L.dn_pi_recon_size():
+            raise RuntimeError("reconstruction table layout mismatch with the kernel library")
+        self.n = len(records)
+        rec = (PiRecon * max(self.n, 1))()
+        start = 0
+        for c, (G, P, Q, out_f, in_f, r) in zip(rec, records):
+            c.G, c.P, c.Q = G, P, Q
+            c.out, c.inn, c.r, c.start = out_f, in_f, r, start
+            start += out_f * in_f
+        self.total = start
+        self._host = rec  # (the launcher reads the tile prefix from the host copy)
+        self._addr = ctypes.addressof(rec)
+        self.table = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8).to(device)
+
+    def run(self, stride: int, world: int):
+        """Reconstruct every layer from ``world`` sites' factors, ``stride`` floats apart."""
+        _lib.call("dn_pi_reconstruct", self.table.data_ptr(), self._addr, self.n, self.total,
+                  int(stride), int(world), _lib.stream())

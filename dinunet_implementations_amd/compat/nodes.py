@@ -71,6 +71,13 @@ class LocalNode:
                              "(runtime.site) from every site's label counts; the COINSTAC phase "
                              "machines need the explicit list of class weights")
         for c in (self.cfg, {**self.cfg, **(self.cfg.get("pretrain_args") or {})}):
+            # the file transport ships engine.payload(), which the private release (issued by
+            # DSGDEngine.reduce on the collective path) never sees
+            from ..parallel.engines import dp_options
+            if dp_options(c)[0] > 0:
+                raise ValueError("dp_clip_norm (the private gradient release) is implemented by "
+                                 "the in-process runtime (runtime.site); the COINSTAC phase "
+                                 "machines would ship the gradient as computed")
             # the phase machines neither know a phase's length in updates when the optimizer
             # is built nor carry a plateau counter between rounds
             if float(c.get("lr_plateau_factor") or 0) > 0:

@@ -96,6 +96,16 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     # (ops.HeadSpec)
     "class_weights": None,
     "label_smoothing": 0,
+    # differentially private gradient release (ops.dp, dSGD only): every gradient a site
+    # releases is clipped to L2 norm dp_clip_norm (0 = off) and gets Gaussian noise of standard
+    # deviation dp_noise_multiplier * dp_clip_norm, on the device, before it leaves the site;
+    # logs.json reports (epsilon, dp_delta) per site (parallel.privacy).  dp_seed: the noise
+    # generator's key (None: the fold's site seed).  pretrain_args may override the first two.
+    # Where they are unset (0), DINUNET_DP_CLIP_NORM / DINUNET_DP_NOISE apply
+    "dp_clip_norm": 0,
+    "dp_noise_multiplier": 0,
+    "dp_delta": 1e-5,
+    "dp_seed": None,
     "rccl_algo": None,
     "rccl_proto": None,
     "collective_timeout_s": 1800,
@@ -337,6 +347,28 @@ def lr_schedule_of(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
             "decay_steps": None if T is None else int(T), "lr_min": float(cfg.get("lr_min") or 0.0)}
 
 
+def check_dp(cfg: Dict[str, Any]) -> None:
+    """The private-release keys of ``cfg`` (normalised in place)."""
+    for key in ("dp_clip_norm", "dp_noise_multiplier"):
+        v = cfg.get(key)
+        v = 0 if v is None else v
+        if not _is_num(v) or not (0 <= v <= 3.4e38):
+            raise ValueError(f"{key} must be a finite number >= 0 (0 = off), got {v!r}")
+        cfg[key] = v
+    if cfg["dp_noise_multiplier"] > 0 and not cfg["dp_clip_norm"] > 0:
+        raise ValueError("dp_noise_multiplier > 0 needs dp_clip_norm > 0 (the noise is scaled by "
+                         "the clip threshold)")
+    d = cfg.get("dp_delta")
+    d = 1e-5 if d is None else d
+    if not _is_num(d) or not (0 < d < 1):
+        raise ValueError(f"dp_delta must lie in (0, 1), got {d!r}")
+    cfg["dp_delta"] = d
+    sd = cfg.get("dp_seed")
+    if sd is not None and (not _is_int(sd) or not (0 <= sd < 2 ** 64)):
+        raise ValueError(f"dp_seed must be an integer >= 0 (or None: the fold's site seed), "
+                         f"got {sd!r}")
+
+
 def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     eng = cfg.get("agg_engine")
     if eng not in ("dSGD", "rankDAD", "powerSGD"):
@@ -357,6 +389,9 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     check_lr_schedule(cfg)
     if isinstance(cfg.get("pretrain_args"), dict):  # the pretraining phase may override each key
         check_lr_schedule({**cfg, **cfg["pretrain_args"]})
+    check_dp(cfg)
+    if isinstance(cfg.get("pretrain_args"), dict):
+        check_dp({**cfg, **cfg["pretrain_args"]})
     ls = cfg.get("label_smoothing", 0)
     ls = 0 if ls is None else ls
     if isinstance(ls, bool) or not isinstance(ls, (int, float)) or not (0 <= ls < 1):

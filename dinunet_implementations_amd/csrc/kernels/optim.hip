@@ -2,6 +2,7 @@
 // into it), so a whole optimizer step is a single launch regardless of the parameter count.
 #include "common.h"
 #include "prologue.h"
+#include "sqnorm.h"
 
 namespace {
 
@@ -10,7 +11,7 @@ namespace {
 // fp64 partial sums of g^2 (a fixed grid, so every partial is rewritten by every launch and the
 // same data always gives the same bits); the Adam launch that follows sums them in the prologue of
 // every updating wave -- no finalize launch, no float atomics, no "last workgroup" ticket.
-constexpr int CLIP_PARTS = 256;  // one workgroup per CU; ~4 float4 per thread at 1 M elements
+constexpr int CLIP_PARTS = SQNORM_PARTS;  // (sqnorm.h: the partials and their fixed order)
 struct ClipState {
   double part[CLIP_PARTS];
   float max_norm;  // threshold c (host-written; read here, so a captured graph follows it)
@@ -19,25 +20,9 @@ struct ClipState {
   int pad;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double x) {  // fixed butterfly: all lanes agree
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
-}
-
 __global__ void __launch_bounds__(256)
 grad_sqnorm_kernel(const float* __restrict__ g, long n4, ClipState* __restrict__ cs) {
-  __shared__ double wsum[4];
-  double acc = 0.0;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc += (double)gg[e] * (double)gg[e];
-  }
-  acc = wave_sum_f64(acc);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) cs->part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  sqnorm_partial(g, n4, cs->part);
 }
 
 // Prologue of a clipped update (all 64 lanes of the wave active): the partials summed in one
@@ -45,9 +30,7 @@ grad_sqnorm_kernel(const float* __restrict__ g, long n4, ClipState* __restrict__
 // into the gradient scale, rounded to fp32 once.  G <= c gives grad_scale back exactly.  A
 // non-finite G sets skip; workgroup 0 records G and counts the skip.
 __device__ __forceinline__ float clip_coef(ClipState* __restrict__ cs, float grad_scale, bool& skip) {
-  const int l = threadIdx.x & 63;
-  const double s = wave_sum_f64((cs->part[l] + cs->part[l + 64]) +
-                                (cs->part[l + 128] + cs->part[l + 192]));
+  const double s = sqnorm_total(cs->part);
   const double G = (double)grad_scale * sqrt(s);
   const float Gf = (float)G;
   skip = !(fabsf(Gf) <= 3.402823466e+38f);  // inf or NaN

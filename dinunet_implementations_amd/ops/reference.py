@@ -151,3 +151,75 @@ def adam_(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, beta1: float
     denom = (exp_avg_sq.sqrt() / (bc2 ** 0.5)).add_(eps)
     params.addcdiv_(exp_avg, denom, value=-lr / bc1)
     return params
+
+
+# ---- differentially private gradient release (csrc/kernels/dp.hip) --------------------------------
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11): ``counter`` four and ``key`` two 32-bit words (ints
+    or equal-shaped integer arrays); the four output words as a uint32 numpy array ``[4, ...]``."""
+    import numpy as np
+    m32 = np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (np.asarray(w, dtype=np.uint64) & m32 for w in counter)
+    k0, k1 = (np.asarray(w, dtype=np.uint64) & m32 for w in key)
+    for _ in range(10):
+        p0 = np.uint64(_PHILOX_M0) * c0  # (< 2^64: both factors are 32-bit)
+        p1 = np.uint64(_PHILOX_M1) * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32,
+                          (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32)
+        k0 = (k0 + np.uint64(_PHILOX_W0)) & m32
+        k1 = (k1 + np.uint64(_PHILOX_W1)) & m32
+    return np.stack(np.broadcast_arrays(c0, c1, c2, c3)).astype(np.uint32)
+
+
+def dp_noise(n: int, seed: int, stream: int, t: int) -> Tensor:
+    """The ``n`` (a multiple of 4) standard normals of release ``t`` (1-based) as dp.hip draws
+    them, in fp64: float4 ``i`` is one Philox call at counter ``(i, t_lo, t_hi, stream)``, key
+    ``(seed_lo, seed_hi)``; outputs ``x_k`` give ``u_k = ((x_k >> 8) + 1) 2^-24`` in (0, 1] and
+    the normals ``r0 cos(2 pi u1), r0 sin(2 pi u1), r1 cos(2 pi u3), r1 sin(2 pi u3)`` with
+    ``r0 = sqrt(-2 ln u0)``, ``r1 = sqrt(-2 ln u2)``."""
+    import numpy as np
+    n, seed, stream, t = int(n), int(seed), int(stream), int(t)
+    if n % 4 or n < 0:
+        raise ValueError("dp_noise: n must be a multiple of 4")
+    i4 = np.arange(n // 4, dtype=np.uint64)
+    x = philox4x32_10((i4, t & 0xFFFFFFFF, (t >> 32) & 0xFFFFFFFF, stream & 0xFFFFFFFF),
+                      (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    u = ((x >> np.uint32(8)).astype(np.float64) + 1.0) * 2.0 ** -24
+    r0, r1 = np.sqrt(-2.0 * np.log(u[0])), np.sqrt(-2.0 * np.log(u[2]))
+    a0, a1 = 2.0 * np.pi * u[1], 2.0 * np.pi * u[3]
+    z = np.stack([r0 * np.cos(a0), r0 * np.sin(a0), r1 * np.cos(a1), r1 * np.sin(a1)], axis=1)
+    return torch.from_numpy(z.reshape(-1))
+
+
+def dp_coef(grad: Tensor, clip_norm: float):
+    """``(coef, G)`` of the release's clip: ``G = ||grad||_2`` from an fp64 sum of squares, ``coef
+    = min(1, c / (G + 1e-6))`` rounded to fp32 once with ``c`` the fp32 device word (``G <= c``:
+    exactly 1); both as Python doubles, ``G`` unrounded."""
+    c = float(torch.tensor(float(clip_norm), dtype=torch.float32))
+    G = float(grad.detach().double().square().sum()) ** 0.5 if grad.numel() else 0.0
+    if G != G or G in (float("inf"), float("-inf")):
+        return float("nan"), G
+    return float(torch.tensor(min(1.0, c / (G + 1e-6)), dtype=torch.float32)), G
+
+
+def dp_privatize(grad: Tensor, clip_norm: float, noise_multiplier: float, seed: int,
+                 stream: int, t: int) -> Tensor:
+    """Release ``t`` (1-based) of ``grad`` (fp32, numel a multiple of 4) as dp.hip computes it,
+    in fp64: ``coef * grad + (sigma c) z`` with :func:`dp_coef`'s ``coef``, :func:`dp_noise`'s
+    ``z`` and ``sigma``, ``c`` the fp32 device words.  A norm that is not finite in fp32 gives all
+    NaN (the release carries nothing); ``sigma == 0`` adds nothing."""
+    flat = grad.detach().reshape(-1).cpu()
+    c = float(torch.tensor(float(clip_norm), dtype=torch.float32))
+    s = float(torch.tensor(float(noise_multiplier), dtype=torch.float32))
+    coef, G = dp_coef(flat, c)
+    Gf = float(torch.tensor(G, dtype=torch.float32))
+    if Gf != Gf or Gf in (float("inf"), float("-inf")):
+        return torch.full(flat.shape, float("nan"), dtype=torch.float64).view(grad.shape)
+    out = flat.double() * coef
+    if s != 0.0:
+        out = out + (s * c) * dp_noise(flat.numel(), seed, stream, t)
+    return out.view(grad.shape)

@@ -32,6 +32,7 @@ import torch.nn as nn
 from ..ops import _grad as _gradreg
 from ..ops import _lib
 from ..ops import capture as _cap
+from ..ops.dp import DPState
 from ..ops.optim import FlatParams
 from .collective import (PAYLOAD_TYPES, SB, DirectMean, from_payload, launch_on, payload_name,
                          payload_numel, to_payload)
@@ -44,9 +45,28 @@ Tensor = torch.Tensor
 
 COLLECTIVES = ("auto", "allreduce", "direct", "peer", "calibrate")
 
+DP_STREAM_RANKS = 2048  # ranks per (fold, phase) in the generator's stream word
+
+
+def dp_options(cfg: dict) -> Tuple[float, float]:
+    """``(dp_clip_norm, dp_noise_multiplier)`` of ``cfg``; where a key is unset (None / 0) the
+    ``DINUNET_DP_CLIP_NORM`` / ``DINUNET_DP_NOISE`` switch applies.  Clip 0: the option is off."""
+    c = float(cfg.get("dp_clip_norm") or os.environ.get("DINUNET_DP_CLIP_NORM", "") or 0)
+    s = float(cfg.get("dp_noise_multiplier") or os.environ.get("DINUNET_DP_NOISE", "") or 0)
+    if not (0.0 <= c <= 3.4e38) or not (0.0 <= s <= 3.4e38):
+        raise ValueError(f"dp_clip_norm / dp_noise_multiplier must be finite numbers >= 0, got "
+                         f"{c!r} / {s!r}")
+    if s > 0 and not c > 0:
+        raise ValueError("dp_noise_multiplier > 0 needs dp_clip_norm > 0 (the noise is scaled by "
+                         "the clip threshold)")
+    return c, s
+
 
 class Engine:
     name = "base"
+    # does the engine release a gradient (ops.dp can privatise it)?  The low-rank engines share
+    # factors / activations instead
+    supports_dp = False
 
     def __init__(self, model: nn.Module, flat: FlatParams, group: SiteGroup, cfg: Optional[dict] = None):
         self.model = model
@@ -70,6 +90,26 @@ class Engine:
             raise ValueError(f"dsgd_collective {coll!r}: expected one of {', '.join(COLLECTIVES)}")
         self.collective = coll
         self.peer = self._want_peer(coll)
+        # differentially private release (ops.dp): on / off is fixed here.  The generator's
+        # stream word fold * 4096 + phase * 2048 + global rank (phase 1: pretraining) keeps every
+        # (site, fold, phase, release) on a counter of its own; ``dp_fold`` / ``dp_phase`` come
+        # from the site loop
+        self.dp: Optional[DPState] = None
+        c, sigma = dp_options(self.cfg)
+        if c > 0:
+            if not self.supports_dp:
+                raise ValueError(f"dp_clip_norm: the private gradient release is implemented for "
+                                 f"dSGD only ({self.name} shares factors, not a gradient)")
+            # (``dp_rank``: the global rank of a site that trains alone in a group of its own)
+            rank = int(self.cfg.get("dp_rank", group.rank))
+            if not (0 <= rank < DP_STREAM_RANKS):
+                raise ValueError(f"dp_clip_norm: rank {rank} does not fit the generator's "
+                                 f"stream word (< {DP_STREAM_RANKS} ranks)")
+            seed = self.cfg.get("dp_seed")
+            seed = int(self.cfg.get("seed", 0) or 0) if seed is None else int(seed)
+            stream = (int(self.cfg.get("dp_fold", 0)) * 2 * DP_STREAM_RANKS
+                      + int(bool(self.cfg.get("dp_phase", 0))) * DP_STREAM_RANKS + rank)
+            self.dp = DPState(flat.grad.device, c, sigma, seed, stream)
 
     def _peer_ok(self) -> bool:
         from . import peer as _peer
@@ -183,6 +223,7 @@ class DSGDEngine(Engine):
     own stream, while autograd keeps computing earlier layers.
     """
     name = "dSGD"
+    supports_dp = True
 
     def __init__(self, model, flat, group, cfg=None, bucket_mb: Optional[float] = None,
                  overlap: bool = True):
@@ -250,6 +291,14 @@ class DSGDEngine(Engine):
         self._peer_build()
         self._hooks = []
         self._delivered = set()
+        self.early_launches = 0  # buckets started before reduce() (observability)
+        self._in_reduce = False
+        if self.dp is not None:
+            # nothing leaves the site before reduce() has privatised the gradient: no hook-issued
+            # launches, no split for the sake of an early bucket, and launch_bucket only records
+            # readiness (as the peer path already behaves)
+            self.overlap = False
+            self.prefers_split = False
         if self.peer:
             # no pushes from autograd's gradient hooks: they run in the autograd thread, on a
             # stream that need not be the step's, and the peer exchange reuses its slots safely
@@ -490,9 +539,12 @@ class DSGDEngine(Engine):
         ordered after the current stream)."""
         if self.group.distributed:
             self._ready[b] = True
-            self._drain()
+            if self.dp is None:  # (private release: the buckets start in reduce())
+                self._drain()
 
     def _launch(self, b: int):
+        if not self._in_reduce:
+            self.early_launches += 1
         if not self._handles:  # first bucket of this step
             self.comm_bytes = 0
         s, e = self.buckets[b]
@@ -535,11 +587,17 @@ class DSGDEngine(Engine):
 
     def reduce(self) -> float:
         g = self.group
+        if self.dp is not None:  # before any byte of the gradient leaves (one site too)
+            self.dp.privatize_(self.flat.grad)
         if not g.distributed:
             self._reset()
             return 1.0
         self._ready = [True] * len(self.buckets)
-        self._drain()
+        self._in_reduce = True
+        try:
+            self._drain()
+        finally:
+            self._in_reduce = False
         if self.peer:  # every pushed bucket's reduce + unpack, in bucket order, fused launches
             from . import peer as _peer
             _peer.finish_many([(h.pm, h.view, h.scale) for h in self._handles.values()])
@@ -561,8 +619,18 @@ class DSGDEngine(Engine):
         self._hooks.clear()
         _gradreg.unregister(self._on_grad)
 
+    def state_dict(self):
+        return {} if self.dp is None else {"dp": self.dp.state_dict()}
+
+    def load_state_dict(self, sd):
+        if self.dp is not None and sd.get("dp"):
+            self.dp.load_state_dict(sd["dp"])
+
     # file transport
     def payload(self):
+        if self.dp is not None:  # (compat/nodes.py refuses the option before it gets here)
+            raise RuntimeError("dSGD payload(): the private gradient release runs in reduce(); "
+                               "the file transport would ship the gradient as computed")
         g = self.flat.grad
         return {"grad": g.to(PAYLOAD_TYPES[self.wire][1]) if self.half else g.clone()}
 
@@ -1093,4 +1161,7 @@ def make_engine(name: str, model: nn.Module, flat: FlatParams, group: SiteGroup,
         cls = ENGINES[name]
     except KeyError:
         raise ValueError(f"unknown agg_engine {name!r}; expected one of {sorted(ENGINES)}")
+    if not cls.supports_dp and dp_options(dict(cfg or {}))[0] > 0:
+        raise ValueError(f"dp_clip_norm: the private gradient release is implemented for dSGD "
+                         f"only, not agg_engine {name!r} (it shares factors, not a gradient)")
     return cls(model, flat, group, cfg)

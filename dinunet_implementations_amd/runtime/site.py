@@ -421,6 +421,7 @@ class FederatedSite:
                     int(trainer.optimizer.skipped_steps))
             if sched_on:  # the rate the epoch's last update used
                 logs.setdefault(f"{tag}learning_rate", []).append(float(opt.applied_lr))
+            self._dp_log(engine, cfg, logs, tag)
             tl.append([round(avg.average, 6)] + met.get((monitor if monitor != "loss" else "auc",)))
             logs.setdefault(f"{tag}samples_per_sec", []).append(nsamp / dt if dt > 0 else 0.0)
             stop = False
@@ -479,7 +480,48 @@ class FederatedSite:
         logs[f"{tag}best_val_score"] = best["score"]
         if step is not None and step.timers.summary():
             logs[f"{tag}phase_ms"] = step.timers.summary()  # DINUNET_PHASE_TIMERS=1
+        self._dp_log(engine, cfg, logs, tag, final=True)
         return best
+
+    def _dp_engine_cfg(self, cfg: Dict[str, Any], fold: int, seed: int, phase: int) -> Dict[str, Any]:
+        """``cfg`` for an engine of this fold and phase (1: pretraining): what the private
+        release's generator needs to keep every (site, fold, phase) on a stream of its own
+        (``parallel.engines.Engine``); ``dp_seed`` defaults to the fold's site seed."""
+        out = dict(cfg, dp_fold=int(fold), dp_phase=int(phase), dp_rank=self.group.rank)
+        if out.get("dp_seed") is None:
+            out["dp_seed"] = int(seed)
+        return out
+
+    def _dp_log(self, engine, cfg: Dict[str, Any], logs: Dict[str, Any], tag: str,
+                final: bool = False):
+        """Private release on (``engine.dp``): per epoch ``dp_epsilon`` (of everything this site
+        has released in this fold so far) and ``dp_grad_norm`` (the last release's pre-clip norm);
+        at the end of a phase the ``dp`` block (pretraining: ``dp_pretrain``).  The pretraining
+        site's releases of both phases count: rho adds across them, epsilon comes from the total
+        (``parallel.privacy``)."""
+        dp = getattr(engine, "dp", None)
+        if dp is None:
+            return
+        from ..parallel import privacy
+        delta = float(cfg.get("dp_delta") or 1e-5)
+        prior = (logs.get("dp_pretrain") or {}) if not tag else {}
+        T, sigma = dp.releases, dp.noise_multiplier
+        rho = privacy.rho(T, sigma) + privacy.rho(int(prior.get("releases", 0)),
+                                                  float(prior.get("noise_multiplier", 0.0)))
+        eps = privacy.loggable(privacy.epsilon_of_rho(rho, delta))
+        if not final:
+            logs.setdefault(f"{tag}dp_epsilon", []).append(eps)
+            logs.setdefault(f"{tag}dp_grad_norm", []).append(dp.last_norm)
+            return
+        block = {"clip_norm": dp.clip_norm, "noise_multiplier": sigma, "delta": delta,
+                 "adjacency": privacy.ADJACENCY, "releases": T, "clipped": dp.clipped,
+                 "nonfinite": dp.nonfinite, "epsilon": eps}
+        if tag:
+            logs["dp_pretrain"] = block
+            return
+        for k in ("releases", "clipped", "nonfinite"):
+            block[k] += int(prior.get(k, 0))
+        logs["dp"] = block
 
     def _device_feed(self, trainer: NNTrainer, step, engine, tr: DeviceLoader, bs: int, li: int,
                      steps: int, cfg: Dict[str, Any], fault_at) -> Optional[DeviceFeed]:
@@ -511,7 +553,8 @@ class FederatedSite:
                 return None
         return DeviceFeed(step, X, tr.labels, bs, steps, col=col)
 
-    def _pretrain(self, trainer: NNTrainer, data, fold_dir: str, seed: int, logs: Dict[str, Any]):
+    def _pretrain(self, trainer: NNTrainer, data, fold_dir: str, seed: int, logs: Dict[str, Any],
+                  fold: int = 0):
         if self.group.replicas > 1:
             raise NotImplementedError("pretrain with several GPUs per site: the pretraining "
                                       "site trains alone (one process)")
@@ -536,7 +579,8 @@ class FederatedSite:
                         lr=float(pa.get("learning_rate", trainer.optimizer.lr)), cache=pcfg)
                 else:
                     trainer.optimizer.lr = float(pa.get("learning_rate", trainer.optimizer.lr))
-                eng = DSGDEngine(trainer.modules(), trainer.flat, solo, pcfg, overlap=False)
+                eng = DSGDEngine(trainer.modules(), trainer.flat, solo,
+                                 self._dp_engine_cfg(pcfg, fold, seed, 1), overlap=False)
                 eng.name = "dSGD-local"
                 self.log(f"pretraining alone on {sizes[src]} samples for {pa.get('epochs')} epochs")
                 b = self._train_epochs(trainer, eng, data, pcfg, solo, fold_dir, seed, logs,
@@ -652,9 +696,9 @@ class FederatedSite:
                     logs.setdefault(k, v)
                 self.log(f"resuming fold {fold} at epoch {start_epoch}")
             elif cfg.get("pretrain"):
-                self._pretrain(trainer, data, fdir, seed, logs)
+                self._pretrain(trainer, data, fdir, seed, logs, fold)
             engine = make_engine(str(cfg.get("agg_engine", "dSGD")), trainer.modules(), trainer.flat,
-                                 self.group, cfg)
+                                 self.group, self._dp_engine_cfg(cfg, fold, seed, 0))
             cal = getattr(engine, "calibration", None)
             if cal:  # dsgd_collective="calibrate": what was measured and chosen
                 logs["dsgd_collective"] = cal

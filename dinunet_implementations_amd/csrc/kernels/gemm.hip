@@ -1165,6 +1165,10 @@ __global__ void __launch_bounds__(256) gemm_splitk_reduce(GemmGroup g) {
 }
 
 static int g_gemm_dma = 1;  // bf16 x bf16 aligned groups take gemm_dma_kernel (A/B switch)
+// set by dn_gemm_grouped for one launch of 64 x 64 tiles: the split-K slabs are written, the
+// reduce launch is left to the caller (the packing Adam sums the partials, optim.hip slab_grad)
+static int g_defer_reduce = 0;
+static int g_reduce_launches = 0;  // gemm_splitk_reduce launches of this process
 // largest grid (workgroups) of 64 x 64 tiles that takes the 8-stage ring (DN_GEMM_RING8_MAX; default
 // 0 = off: measured slower at the B = 32 step, encoder 10.2 vs 9.2 us and input gradient 15.5 vs
 // 14.2 -- those K loops are not bound by the tiles in flight, 0.3146 vs 0.3116 ms/step)
@@ -1237,10 +1241,11 @@ int launch(GemmGroup& g, hipStream_t st) {
     hipLaunchKernelGGL((gemm_kernel<BM, BN, TA, TB, TAe, TBe, true>), grid, dim3(256), 0, st, g);
   else
     hipLaunchKernelGGL((gemm_kernel<BM, BN, TA, TB, TAe, TBe, false>), grid, dim3(256), 0, st, g);
-  if (g.splits > 1 && !g.cnt) {
+  if (g.splits > 1 && !g.cnt && !(BM == 64 && g_defer_reduce)) {
     const long t4 = elems / 4;
     const int blocks = (int)((t4 + 255) / 256 < 4096 ? (t4 + 255) / 256 : 4096);
     hipLaunchKernelGGL(gemm_splitk_reduce, dim3(blocks), dim3(256), 0, st, g);
+    ++g_reduce_launches;
   }
   return dn_launch_status();
 }
@@ -1279,6 +1284,7 @@ static int launch256(GemmGroup& g, int ta, int tb, hipStream_t st) {
     const long t4 = elems / 4;
     const int blocks = (int)((t4 + 255) / 256 < 4096 ? (t4 + 255) / 256 : 4096);
     hipLaunchKernelGGL(gemm_splitk_reduce, dim3(blocks), dim3(256), 0, st, g);
+    ++g_reduce_launches;
   }
   return dn_launch_status();
 }
@@ -1388,6 +1394,9 @@ DN_API int dn_gemm_set_dma(int on) {
 // the current dn_gemm_set_dma setting (1: LDS-DMA kernel)
 DN_API int dn_gemm_dma_on() { return g_gemm_dma; }
 
+// gemm_splitk_reduce launches issued so far (a launch whose reduce was deferred adds none)
+DN_API int dn_gemm_reduce_launches() { return g_reduce_launches; }
+
 // Output tiles of a launch (the split-K ticket count `counters` must provide): 64x64 tiles
 // (tile 0) or 128x128 (tile 1) summed over the problems.
 DN_API long dn_gemm_tiles(int n, const int* M, const int* N, int tile) {
@@ -1433,6 +1442,9 @@ DN_API int dn_gemm(const void* A, int a_bf16, int ta, long lda, const void* B, i
 // output type in ONE launch (+ one split-K reduce).  Per-problem arrays (`ncol` may be null: see
 // Epi::ncol); `slab` holds
 // splits * sum(M_i * N_i) fp32 when splits > 1.  Every problem uses the same K split count.
+// defer_reduce: a split launch of 64 x 64 tiles (tile 0, no tickets) writes its slabs -- problem i
+// at slab + splits * sum_{j<i} M_j N_j, [splits][M_i][N_i] -- and launches no reduce: the caller
+// owns the combine and the epilogue (alpha, beta, row maps, column sums).
 DN_API int dn_gemm_grouped(int n, const void* const* A, const long* lda, const void* const* B,
                            const long* ldb, void* const* C, const long* ldc, const int* M,
                            const int* N, const int* K, const float* alpha, const float* beta,
@@ -1441,9 +1453,11 @@ DN_API int dn_gemm_grouped(int n, const void* const* A, const long* lda, const v
                            void* const* X1, void* const* X2, const int* perm, int relu,
                            int a_bf16, int b_bf16, int ta, int tb, int c_bf16, int tile,
                            int splits, float* slab, int* counters, void* const* GX,
-                           void* const* SUBJ, const int* GS, const int* GOP, hipStream_t st) {
+                           void* const* SUBJ, const int* GS, const int* GOP, int defer_reduce,
+                           hipStream_t st) {
   if (n < 1 || n > GMAX) return DN_BAD_SHAPE;
   if (splits > 1 && !slab) return DN_BAD_SHAPE;
+  if (defer_reduce && (splits <= 1 || tile != 0 || counters)) return DN_BAD_SHAPE;
   GemmGroup g;
   g.cnt = splits > 1 ? counters : nullptr;
   g.perm = perm;
@@ -1472,5 +1486,8 @@ DN_API int dn_gemm_grouped(int n, const void* const* A, const long* lda, const v
                             P.epi.ncol > 0 || bias[i]))
       return DN_BAD_SHAPE;  // the ones column is the last one, fp32 outputs
   }
-  return run_group(g, a_bf16, b_bf16, ta, tb, tile, st);
+  g_defer_reduce = defer_reduce != 0;
+  const int rc = run_group(g, a_bf16, b_bf16, ta, tb, tile, st);
+  g_defer_reduce = 0;
+  return rc;
 }

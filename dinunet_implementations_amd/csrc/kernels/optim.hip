@@ -252,6 +252,102 @@ __device__ __forceinline__ void pack_store4(const PackPlan& pl, const PackSeg& s
   for (int e = 0; e < 4; ++e) pack_store(pl, sg, j0 + e, v[e]);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Split-K slab sources (FusedAdam.step_pack with the step's deferred weight-gradient launch
+// armed, ops._grad.arm_slabs): the gradient of a segment is not read from g but summed here from
+// the fp32 partials [splits][M][N] the grouped weight-gradient GEMM left (gemm.hip
+// dn_gemm_grouped defer_reduce), operation for operation what gemm_splitk_reduce + epi_store4 /
+// epi_store would have stored into g -- the reduce launch and its pass over g disappear.
+//   SRC_ROWS  segment element j = (row, k) of [rows][N]: slab element (m, k), 16-B loads
+//             (N % 4 == 0); splits summed four at a time, v += ((a0 + a1) + a2) + a3, then the
+//             rest one by one (the reduce's vector path)
+//   SRC_COL   segment element j = row of a column sum (a bias gradient as its own a^T @ ones
+//             problem, one column stored): slab element (m, 0); splits summed in order (the
+//             reduce's scalar path)
+//   SRC_GATE  m = 4u + g of reference row g * Hd + u (the inverse of the LSTM row map, which
+//             pack_store4 computes too), else m = row
+// then v *= alpha and v += beta * 0: the reduce accumulated into the zero this kernel wrote one
+// step earlier, and the add is kept so that a -0 sum ends as the +0 it did there.
+enum SlabMode { SRC_ROWS = 1, SRC_COL = 2, SRC_GATE = 4 };
+struct SlabSrc {
+  const float* slab;  // null: the segment reads g
+  long elems;         // fp32 elements the allocation holds from `slab` on (host check)
+  int M, N, splits, mode;
+  float alpha, beta;
+};
+struct SlabPlan {
+  SlabSrc s[PACK_SEGS];  // by segment
+};
+
+// the gradient of segment elements j0 .. j0 + 3 (j0 % 4 == 0, j0 + 3 < sg.n, sg.n % 4 == 0)
+__device__ __forceinline__ f32x4 slab_grad(const PackPlan& pl, const SlabSrc& sr, int j0) {
+  const long mn = (long)sr.M * sr.N;
+  const bool gate = (sr.mode & SRC_GATE) != 0;
+  f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (sr.mode & SRC_COL) {
+    long at[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      int r = j0 + e;
+      if (gate) {
+        const int g = r / pl.Hd, u = r - g * pl.Hd;
+        r = 4 * u + g;
+      }
+      at[e] = (long)r * sr.N;
+    }
+    for (int s = 0; s < sr.splits; ++s) {  // the four rows' loads of a split issue together
+      const float* b = sr.slab + (long)s * mn;
+      const float a0 = b[at[0]], a1 = b[at[1]], a2 = b[at[2]], a3 = b[at[3]];
+      v[0] += a0;
+      v[1] += a1;
+      v[2] += a2;
+      v[3] += a3;
+    }
+  } else {
+    int row = j0 / sr.N;
+    const int k = j0 - row * sr.N;
+    if (gate) {
+      const int g = row / pl.Hd, u = row - g * pl.Hd;
+      row = 4 * u + g;
+    }
+    const float* b = sr.slab + (long)row * sr.N + k;
+    int s = 0;
+    for (; s + 4 <= sr.splits; s += 4) {  // four slab loads in flight per round
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(b + (long)s * mn);
+      const f32x4 a1 = *reinterpret_cast<const f32x4*>(b + (long)(s + 1) * mn);
+      const f32x4 a2 = *reinterpret_cast<const f32x4*>(b + (long)(s + 2) * mn);
+      const f32x4 a3 = *reinterpret_cast<const f32x4*>(b + (long)(s + 3) * mn);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] += ((a0[e] + a1[e]) + a2[e]) + a3[e];
+    }
+    // the remainder (the headline's 3 splits are all remainder): loads issued together, added
+    // one by one in split order
+    const int rem = sr.splits - s;
+    if (rem == 3) {
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(b + (long)s * mn);
+      const f32x4 a1 = *reinterpret_cast<const f32x4*>(b + (long)(s + 1) * mn);
+      const f32x4 a2 = *reinterpret_cast<const f32x4*>(b + (long)(s + 2) * mn);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = ((v[e] + a0[e]) + a1[e]) + a2[e];
+    } else if (rem == 2) {
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(b + (long)s * mn);
+      const f32x4 a1 = *reinterpret_cast<const f32x4*>(b + (long)(s + 1) * mn);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = (v[e] + a0[e]) + a1[e];
+    } else if (rem == 1) {
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(b + (long)s * mn);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] += a0[e];
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] *= sr.alpha;
+    if (sr.beta != 0.f) v[e] += sr.beta * 0.f;
+  }
+  return v;
+}
+
 // Per-step train-metric record of a device-fed epoch (runtime.feed.DeviceFeed): the step's score
 // column out[b][col] (ICA: prob[:, 1], reference comps/icalstm/__init__.py:64-65) and its loss
 // land in rings indexed by the batch cursor, so an epoch of K-step graph replays yields the exact
@@ -279,13 +375,15 @@ __device__ __forceinline__ void record_step(const StepRecord& r, int cofs) {
 
 __global__ void __launch_bounds__(256) record_kernel(StepRecord r, int cofs) { record_step(r, cofs); }
 
-template <bool CLIP, bool SCHED>
+// SLAB: some segments take their gradient from split-K slabs (sl; slab_grad above).  Never with
+// CLIP: the norm needs the finished gradient before this launch.
+template <bool CLIP, bool SCHED, bool SLAB = false>
 __global__ void __launch_bounds__(256)
 adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                  float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
                  float grad_scale, const int* __restrict__ tdev, double b1d, double b2d, int update,
                  int zero_grad, PackPlan pl, StepPrologue sp, int gofs, int ublocks, StepRecord rec,
-                 ClipState* __restrict__ cs, LrState* __restrict__ ls) {
+                 ClipState* __restrict__ cs, LrState* __restrict__ ls, SlabPlan sl) {
   // the step's train record (rec.out set): the LAST workgroup; the cursor was advanced by this
   // step's encoder GEMM, so it names the batch this step trained on
   if (rec.out && blockIdx.x == gridDim.x - 1) {
@@ -320,8 +418,21 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
   const long n4 = n >> 2, stride = (long)ublocks * blockDim.x;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+    const long e0 = i << 2;
+    int s = 0;
+    if constexpr (SLAB) {  // the element's segment first: it says where the gradient comes from
+      while (s < pl.cnt && e0 >= pl.s[s].off + pl.s[s].n) ++s;
+    }
     if (update) {
-      const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+      f32x4 gg;
+      if constexpr (SLAB) {
+        if (s < pl.cnt && e0 >= pl.s[s].off && sl.s[s].slab)
+          gg = slab_grad(pl, sl.s[s], (int)(e0 - pl.s[s].off));
+        else
+          gg = reinterpret_cast<const f32x4*>(g)[i];
+      } else {
+        gg = reinterpret_cast<const f32x4*>(g)[i];
+      }
       f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
       f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
 #pragma unroll
@@ -336,9 +447,9 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
       reinterpret_cast<f32x4*>(v)[i] = vv;
     }
     if (zero_grad) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const long e0 = i << 2;
-    int s = 0;
-    while (s < pl.cnt && e0 >= pl.s[s].off + pl.s[s].n) ++s;
+    if constexpr (!SLAB) {
+      while (s < pl.cnt && e0 >= pl.s[s].off + pl.s[s].n) ++s;
+    }
     if (s < pl.cnt && e0 >= pl.s[s].off) {
       const PackSeg& sg = pl.s[s];
       const int j0 = (int)(e0 - sg.off);
@@ -443,15 +554,36 @@ DN_API int dn_adam_dev(float* p, const float* g, float* m, float* v, long n, flo
 // adam_pack_kernel launch.  segs: host PackSeg-compatible rows {off, n, kind, d, dst, dst2} sorted
 // by offset (cnt <= 16); the device-fed gather (gx ... yd) is optional (gx null: none).
 DN_API long dn_pack_seg_size() { return (long)sizeof(PackSeg); }
+DN_API long dn_slab_src_size() { return (long)sizeof(SlabSrc); }
+
+// A slab source against its segment: every index slab_grad forms from a segment element stays
+// inside [splits][M][N], and that lies inside what the caller says the allocation holds.
+static bool slab_src_ok(const SlabSrc& r, const PackSeg& s, int Hd, int HD) {
+  if (((uintptr_t)r.slab & 15) || r.M <= 0 || r.N <= 0 || r.splits < 2 || r.splits > 64) return false;
+  if ((long)r.splits * r.M * r.N > r.elems || s.n % 4) return false;
+  const bool gate = (r.mode & SRC_GATE) != 0;
+  const int shape = r.mode & (SRC_ROWS | SRC_COL);
+  if ((r.mode & ~(SRC_ROWS | SRC_COL | SRC_GATE)) || (shape != SRC_ROWS && shape != SRC_COL))
+    return false;
+  // gate rows: reference row g * Hd + u < 4 Hd -> slab row 4 u + g < 4 Hd <= 4 HD = M
+  if (gate && (Hd <= 0 || HD < Hd || r.M != 4 * HD)) return false;
+  const long rows = gate ? 4L * Hd : r.M;
+  if (shape == SRC_ROWS) return r.N % 4 == 0 && s.n == rows * r.N;
+  return s.n == rows;
+}
+
+// srcs: null, or cnt SlabSrc rows by segment (slab null: that segment reads g) -- only with an
+// unclipped update.
 DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr, double b1,
                         double b2, float eps, float wd, float grad_scale, const int* tdev,
                         int update, int zero_grad, const void* segs, int cnt, int I, int Hd,
                         int HD, const void* gx, int gx_bf16, long row_elems, const long long* gy,
                         const long long* order, long nb, const long long* cursor, int B,
                         void* xb, long long* yd, long long* sd, int gofs, const void* record,
-                        void* clip, void* sched, hipStream_t st) {
+                        void* clip, void* sched, const void* srcs, hipStream_t st) {
   if (n <= 0 || n % 4 || cnt < 0 || cnt > PACK_SEGS) return DN_BAD_SHAPE;
   if (clip && !update) return DN_BAD_SHAPE;  // the partials belong to an update's gradient
+  if (srcs && (clip || !update)) return DN_BAD_SHAPE;
   if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
   StepRecord rec{};
   if (record && update) {
@@ -477,6 +609,17 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
       return DN_BAD_SHAPE;
     if (s.kind == PK_WHH && !s.dst2) return DN_BAD_SHAPE;
   }
+  SlabPlan sl{};
+  bool slabs = false;
+  if (srcs) {
+    const SlabSrc* hr = reinterpret_cast<const SlabSrc*>(srcs);
+    for (int k = 0; k < cnt; ++k) {
+      if (!hr[k].slab) continue;
+      if (!slab_src_ok(hr[k], pl.s[k], Hd, HD)) return DN_BAD_SHAPE;
+      sl.s[k] = hr[k];
+      slabs = true;
+    }
+  }
   StepPrologue sp{};
   if (gx) {
     const int rc = prologue_gather(sp, gx, gx_bf16, row_elems, gy, order, nb, cursor, B, xb, yd,
@@ -487,11 +630,12 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
   // rest start as the first retire)
   auto parts = [](long items) { return (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096); };
   const int ub = parts(n / 4), gb = sp.gx ? parts(sp.ux + sp.ny) : 0;
-  hipLaunchKernelGGL(DN_ADAM_PICK(adam_pack_kernel, clip, sched),
-                     dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, p, g, m, v, n, lr,
-                     (float)b1, (float)b2, eps, wd, grad_scale, tdev, b1, b2, update, zero_grad, pl,
-                     sp, gofs, ub, rec, reinterpret_cast<ClipState*>(clip),
-                     reinterpret_cast<LrState*>(sched));
+  auto kernel = DN_ADAM_PICK(adam_pack_kernel, clip, sched);
+  if (slabs) kernel = sched ? adam_pack_kernel<false, true, true> : adam_pack_kernel<false, false, true>;
+  hipLaunchKernelGGL(kernel, dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, p, g, m, v, n,
+                     lr, (float)b1, (float)b2, eps, wd, grad_scale, tdev, b1, b2, update, zero_grad,
+                     pl, sp, gofs, ub, rec, reinterpret_cast<ClipState*>(clip),
+                     reinterpret_cast<LrState*>(sched), sl);
   return dn_launch_status();
 }
 

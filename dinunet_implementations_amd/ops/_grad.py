@@ -18,6 +18,22 @@ _pending_params: List[torch.Tensor] = []
 
 _callbacks: List[Callable[[torch.nn.Parameter], None]] = []
 
+# armed by a step whose fused Adam sums the split-K partials itself (:func:`arm_slabs`)
+_slab_sink = None
+
+
+def arm_slabs(sink) -> None:
+    """Until :func:`disarm_slabs`: :func:`flush` offers ``sink`` (``FusedAdam.slab_sink``) the
+    slab descriptors of every split launch it issues (``ops.gemm.mm_grouped`` ``slab_sink``); a
+    launch the sink accepts leaves its reduce to the optimizer's launch of the same step."""
+    global _slab_sink
+    _slab_sink = sink
+
+
+def disarm_slabs() -> None:
+    global _slab_sink
+    _slab_sink = None
+
 
 def register(cb: Callable[[torch.nn.Parameter], None]) -> None:
     if cb not in _callbacks:
@@ -82,5 +98,5 @@ def flush() -> None:
                q["b"].stride(-1) == 1, q["a"].device)
         groups.setdefault(key, []).append(q)
     for g in groups.values():
-        mm_grouped(g, trans_a=True)
+        mm_grouped(g, trans_a=True, slab_sink=_slab_sink)
     notify(params)

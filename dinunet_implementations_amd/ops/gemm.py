@@ -31,7 +31,14 @@ _lib.register("dn_gemm_dma_on", [])
 _lib.register("dn_gemm_arm_bump", [_lib.c_void_p, _lib.c_void_p])
 _lib.register("dn_gemm_bump_armed", [])
 _lib.register("dn_gemm_grouped", [_lib.c_int] + [_lib.c_void_p] * 19 + [_lib.c_int] * 8
-              + [_lib.c_void_p, _lib.c_void_p] + [_lib.c_void_p] * 4 + [_lib.c_void_p])
+              + [_lib.c_void_p, _lib.c_void_p] + [_lib.c_void_p] * 4 + [_lib.c_int, _lib.c_void_p])
+_lib.register("dn_gemm_reduce_launches", [])
+
+
+def reduce_launches() -> int:
+    """``gemm_splitk_reduce`` launches this process has issued (captured ones count once, at
+    capture): a split launch whose reduce was deferred to the packing Adam adds none."""
+    return int(_lib.lib().dn_gemm_reduce_launches())
 
 # Operands read in place from a dataset resident in HBM (csrc/kernels/gemm.hip RowGather): a
 # registered tensor (the device-fed step's static batch buffer, 2-D [B*S, F]) stands for rows
@@ -426,8 +433,15 @@ def _launch_class(q, trans_a: bool, trans_b: bool):
 
 
 def mm_grouped(problems, trans_a: bool = False, trans_b: bool = False,
-               splits: Optional[int] = None, tile: Optional[int] = None):
+               splits: Optional[int] = None, tile: Optional[int] = None, slab_sink=None):
     """Several independent ``out_i (+)= alpha_i * op(a_i) @ op(b_i)`` in ONE launch.
+
+    ``slab_sink(descs, slab) -> bool``: offered the :class:`ops.slabsrc.SlabDesc` of every problem
+    of a launch that splits K on 64 x 64 tiles with the reduce kernel (not the 128 / 256 tiles,
+    not ``DINUNET_SPLITK_INLAUNCH``) before it is issued.  True: the sink takes over the combine
+    (and must keep ``slab`` alive until it has read it on this stream); the launch then writes its
+    slabs as always and launches no ``gemm_splitk_reduce``.  False keeps the reduce launch; an
+    unsplit launch has no slabs and is not offered.
 
     ``problems``: sequence of dicts with keys ``a``, ``b``, ``out`` (required, fp32 or bf16 like
     every other ``out`` of the group) and optional ``alpha``, ``beta``, ``bias``, ``row_map``,
@@ -451,11 +465,11 @@ def mm_grouped(problems, trans_a: bool = False, trans_b: bool = False,
             classes.setdefault(_launch_class(q, trans_a, trans_b), []).append(q)
         if len(classes) > 1:
             for grp in classes.values():
-                mm_grouped(grp, trans_a, trans_b, splits, tile)
+                mm_grouped(grp, trans_a, trans_b, splits, tile, slab_sink)
             return
     if len(probs) > GMAX:
         for i in range(0, len(probs), GMAX):
-            mm_grouped(probs[i:i + GMAX], trans_a, trans_b, splits, tile)
+            mm_grouped(probs[i:i + GMAX], trans_a, trans_b, splits, tile, slab_sink)
         return
     if not probs[0]["a"].is_cuda:
         for q in probs:
@@ -540,6 +554,19 @@ def mm_grouped(problems, trans_a: bool = False, trans_b: bool = False,
                            dtype=torch.float32, device=dev)
         b_ = 128 if tile in (1, 2) else 64
         cnt = _tickets(dev, sum(-(-m // b_) * -(-nn // b_) for m, nn in zip(arrs["M"], arrs["N"])))
+    defer = 0
+    if slab_sink is not None and sp > 1 and cnt is None and not tile:
+        from .slabsrc import SlabDesc
+        descs, soff = [], 0
+        for i in range(n):
+            descs.append(SlabDesc(
+                slab=slab.data_ptr() + 4 * soff, slab_elems=slab.numel() - soff, M=arrs["M"][i],
+                N=arrs["N"][i], splits=sp, alpha=arrs["alpha"][i], beta=arrs["beta"][i],
+                row_map=arrs["rmap"][i], ncol=arrs["ncol"][i], xcol=arrs["xcol"][i],
+                C=arrs["C"][i], C2=arrs["C2"][i], ldc=arrs["ldc"][i], X1=arrs["X1"][i],
+                X2=arrs["X2"][i]))
+            soff += sp * arrs["M"][i] * arrs["N"][i]
+        defer = int(bool(slab_sink(descs, slab)))
     P = ctypes.c_void_p
     L = ctypes.c_long
     I = ctypes.c_int
@@ -554,7 +581,7 @@ def mm_grouped(problems, trans_a: bool = False, trans_b: bool = False,
               int(a_bf), int(b_bf), ta, tb,
               int(c_bf), 0 if tile is None else int(tile), sp, _lib.ptr(slab), _lib.ptr(cnt),
               (P * n)(*arrs["GX"]), (P * n)(*arrs["SUBJ"]), (I * n)(*arrs["GS"]),
-              (I * n)(*arrs["GOP"]), _lib.stream())
+              (I * n)(*arrs["GOP"]), defer, _lib.stream())
 
 
 # Plain GEMMs (bf16 operands, no row map) run on csrc/kernels/gemm.hip's LDS-DMA kernel, which

@@ -53,7 +53,7 @@ _lib.register("dn_adam_pack", [_lib.c_void_p] * 4 + [_lib.c_long, _lib.c_float, 
                                _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
                                _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
                                _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
-                               _lib.c_void_p, _lib.c_void_p])
+                               _lib.c_void_p, _lib.c_void_p, _lib.c_void_p])
 _lib.register("dn_step_record", [_lib.c_void_p, _lib.c_int, _lib.c_void_p])
 
 
@@ -226,6 +226,7 @@ class FusedAdam:
         self._tdev: Optional[torch.Tensor] = None  # device step counter (graph-captured steps)
         # device-fed batches (ops.DeviceSource): the update advances the source's cursor
         self.cursor: Optional[torch.Tensor] = None
+        self.drop_slabs()
         if max_grad_norm is None:
             env = os.environ.get("DINUNET_MAX_GRAD_NORM", "")
             max_grad_norm = float(env) if env else 0.0
@@ -503,6 +504,58 @@ class FusedAdam:
         if not copy_x and sd is None:
             raise ValueError("attach_pack: without the batch copy the step needs its row indices")
         self._pack = (pack, tab, len(rows), src, xb, yd, sd, copy_x)
+        self._pack_rows = rows
+        self.drop_slabs()
+
+    # split-K slab sources: the update sums the weight-gradient partials itself -------------------
+    def slab_sink(self):
+        """The ``ops._grad.arm_slabs`` sink of a step that ends in :meth:`step_pack`: a split
+        weight-gradient launch whose every problem writes exactly one pack segment's gradient
+        (``ops.slabsrc.match``) skips its ``gemm_splitk_reduce``; :meth:`step_pack` then builds
+        those segments' gradients from the slabs (``optim.hip slab_grad``: the reduce's sums and
+        epilogue, operation for operation) instead of reading ``flat.grad``, which for them still
+        holds the zero the previous update wrote.  Anything else -- clipping (the norm needs the
+        finished gradient first), a descriptor that fits no segment, the 128 / 256 tiles -- is
+        refused and keeps the reduce launch.  The step calls :meth:`drop_slabs` when it ends."""
+        return self._accept_slabs
+
+    def _accept_slabs(self, descs, slab) -> bool:
+        if self._clip is not None or getattr(self, "_pack", None) is None:
+            return False
+        from . import slabsrc
+        from .lstm import _row_map
+        pack = self._pack[0]
+        dev = self.flat.grad.device
+        got = slabsrc.match(descs, self._pack_rows, self.flat.grad.data_ptr(), pack.I, pack.Hd,
+                            pack.HD, _row_map(pack.Hd, pack.HD, dev).data_ptr(),
+                            taken=self._slab_srcs)
+        if got is None:
+            return False
+        self._slab_srcs.update(got)
+        self._slab_keep.append(slab)  # alive, at its address, until step_pack has been issued
+        return True
+
+    def drop_slabs(self):
+        """Forget accepted slab sources (:meth:`step_pack` consumed them, or the step failed)."""
+        self._slab_srcs = {}
+        self._slab_keep = []
+
+    def _slab_table(self, cnt: int):
+        """The ``optim.hip SlabSrc`` rows by segment for the accepted sources."""
+        import ctypes
+
+        class _Src(ctypes.Structure):
+            _fields_ = [("slab", ctypes.c_void_p), ("elems", ctypes.c_long), ("M", ctypes.c_int),
+                        ("N", ctypes.c_int), ("splits", ctypes.c_int), ("mode", ctypes.c_int),
+                        ("alpha", ctypes.c_float), ("beta", ctypes.c_float)]
+        L = _lib.lib()
+        L.dn_slab_src_size.restype = ctypes.c_long
+        if ctypes.sizeof(_Src) != L.dn_slab_src_size():
+            raise RuntimeError("slab source layout mismatch with the kernel library")
+        tab = (_Src * max(1, cnt))()
+        for i, s in self._slab_srcs.items():
+            tab[i] = _Src(s.slab, s.slab_elems, s.M, s.N, s.splits, s.mode, s.alpha, s.beta)
+        return tab
 
     def step_pack(self, grad_scale: float = 1.0, update: bool = True, gofs: int = 1,
                   record=None):
@@ -524,12 +577,22 @@ class FusedAdam:
         else:
             gx = [None, 0, 0, None, None, 1, None, 0, None, None, None]
         clip = self._sqnorm() if update else None
-        _lib.call("dn_adam_pack", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
-                  self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
-                  self.weight_decay, grad_scale, self._tdev.data_ptr(), int(update), 1,
-                  ctypes_addr(tab), cnt, pack.I, pack.Hd, pack.HD, *gx, int(gofs),
-                  ctypes_addr(record) if (record is not None and update) else None, clip,
-                  _lib.ptr(self._lrs), _lib.stream())
+        srcs = None
+        if self._slab_srcs:
+            if not update or clip is not None:
+                raise RuntimeError("FusedAdam.step_pack: slab sources were accepted for a launch "
+                                   "that cannot sum them (no update, or a clipped one)")
+            srcs = self._slab_table(cnt)
+        try:
+            _lib.call("dn_adam_pack", d.data_ptr(), self.flat.grad.data_ptr(),
+                      self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1,
+                      b2, self.eps, self.weight_decay, grad_scale, self._tdev.data_ptr(),
+                      int(update), 1, ctypes_addr(tab), cnt, pack.I, pack.Hd, pack.HD, *gx,
+                      int(gofs), ctypes_addr(record) if (record is not None and update) else None,
+                      clip, _lib.ptr(self._lrs), ctypes_addr(srcs) if srcs is not None else None,
+                      _lib.stream())
+        finally:
+            self.drop_slabs()  # (the launch is in the stream: the slabs may be reused after it)
 
     def device_step(self) -> torch.Tensor:
         """The device step counter (int32[1]) the graph-captured update reads; a step prologue

@@ -35,6 +35,7 @@ from typing import Callable, Optional
 import torch
 
 from .. import ops
+from ..ops import _grad as _gradreg
 from ..ops import _lib
 from ..ops.lstm import defer_pack, ride_pack, run_deferred_pack, use_persistent
 from .timers import NULL, PhaseTimer, enabled_by_env
@@ -107,6 +108,12 @@ ROWS_FEED_MIN_B = 256
 # from the parameters it updates, zeroes the gradient and gathers the next batch (one launch
 # instead of Adam + a pack/gather launch per step); DINUNET_ADAM_PACK=0 keeps the pack launch
 ADAM_PACK = os.environ.get("DINUNET_ADAM_PACK", "1") != "0"
+
+# The single-site captured step with that launch: the grouped weight-gradient GEMM leaves its
+# split-K partials in their slabs and the Adam sums them as it consumes the gradient -- no
+# gemm_splitk_reduce launch, no pass writing flat.grad only for the Adam to read it back
+# (ops.FusedAdam.slab_sink).  DINUNET_ADAM_SLABS=0 keeps the reduce launch (A/B switch)
+ADAM_SLABS = os.environ.get("DINUNET_ADAM_SLABS", "1") != "0"
 
 # Multi-site steps over RCCL capture the engine's collectives inside the step graph
 # (DINUNET_CAPTURE_COMM=0 keeps host-issued collectives between two graph replays)
@@ -573,14 +580,36 @@ class TrainStep:
     def _dev_body_apack(self):
         """One whole device-fed step in the Adam-emitted-pack form (single site)."""
         sx, sy = self._dsxf, self._dsy
-        with self._rows_ctx(), self._apack_forward():
-            out, loss, pred = self._fwd_bwd(sx, sy)
-        if self._pre_reduce is not None:
-            self._pre_reduce()
-        scale = (self.engine.reduce(factorized=True) if self._pre_reduce is not None
-                 else self.engine.reduce())
-        self.opt.step_pack(grad_scale=scale, record=self._rec_args(out, loss, pred))
+        slabs = self._slabs_ok()
+        if slabs:
+            _gradreg.arm_slabs(self.opt.slab_sink())
+        try:
+            try:
+                with self._rows_ctx(), self._apack_forward():
+                    out, loss, pred = self._fwd_bwd(sx, sy)
+            finally:
+                _gradreg.disarm_slabs()  # never leaks into a later launch
+            if self._pre_reduce is not None:
+                self._pre_reduce()
+            scale = (self.engine.reduce(factorized=True) if self._pre_reduce is not None
+                     else self.engine.reduce())
+            self.opt.step_pack(grad_scale=scale, record=self._rec_args(out, loss, pred))
+        finally:
+            self.opt.drop_slabs()
         return out, loss, pred
+
+    def _slabs_ok(self) -> bool:
+        """May this step's Adam sum the split-K weight-gradient partials itself (``ADAM_SLABS``)?
+        Only where nothing reads ``flat.grad`` between the backward and the update: one site on
+        dSGD (no collective, no rank-dAD / PowerSGD factorisation of the gradient), no
+        differentially private release (it clips and perturbs the gradient in place) and no
+        global-norm clipping (its norm launch reads the finished gradient)."""
+        eng, grp = self.engine, self.engine.group
+        return bool(ADAM_SLABS and self._apack is not None and self.accum == 1
+                    and isinstance(self.opt, ops.FusedAdam) and self.opt.max_grad_norm is None
+                    and eng.name == "dSGD" and not grp.distributed
+                    and getattr(grp, "world", 1) == 1 and self._pre_reduce is None
+                    and getattr(eng, "dp", None) is None)
 
     def _rec_args(self, out, loss, pred=None):
         return self.rec.args(out, loss, pred) if self.rec is not None else None

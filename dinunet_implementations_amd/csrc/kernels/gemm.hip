@@ -295,10 +295,14 @@ __device__ __forceinline__ void group_bump(const GemmGroup& g) {
 
 typedef __attribute__((address_space(1))) unsigned gu32;
 
+// ReLU as torch.relu: NaN stays NaN (fmaxf(NaN, 0) is 0, which hid a non-finite activation from
+// the gradient norm that skips the Adam step); a compare and a select, as cheap as the max
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+
 __device__ __forceinline__ void epi_store(const Epi& epi, void* C, long ldc, int row, int col, float v) {
   v *= epi.alpha;
   if (epi.bias) v += epi.bias[col];
-  if (epi.relu) v = fmaxf(v, 0.f);
+  if (epi.relu) v = relu_f(v);
   if (epi.mask && !((float)epi.mask[(long)row * epi.ldm + col] > 0.f)) v = 0.f;
   const long orow = epi.row_map ? epi.row_map[row] : row;
   if (orow < 0) return;  // dropped row (e.g. zero-padded LSTM units)
@@ -810,7 +814,7 @@ gemm_dma_kernel(GemmGroup g) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = acc[i][j][r] * ep.alpha + bias;
-          if (ep.relu) v = fmaxf(v, 0.f);
+          if (ep.relu) v = relu_f(v);
           E[(16 * i + 4 * (lane >> 4) + r) * ES + lc] = v;
         }
     }
@@ -1006,7 +1010,7 @@ gemm256_kernel(GemmGroup g) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float v = acc[2 * pass + i][j][r] * alpha + bias;
-            if (relu) v = fmaxf(v, 0.f);
+            if (relu) v = relu_f(v);
             E[(16 * i + 4 * (lane >> 4) + r) * ES + lc] = v;
           }
       }
@@ -1082,7 +1086,7 @@ __device__ __forceinline__ void epi_store4(const Epi& epi, void* C, long ldc, in
   for (int e = 0; e < 4; ++e) {
     v[e] *= epi.alpha;
     if (epi.bias) v[e] += epi.bias[col + e];
-    if (epi.relu) v[e] = fmaxf(v[e], 0.f);
+    if (epi.relu) v[e] = relu_f(v[e]);
     if (epi.mask && !((float)epi.mask[(long)row * epi.ldm + col + e] > 0.f)) v[e] = 0.f;
   }
   for (int oo = 0; oo < (epi.C2 ? 2 : 1); ++oo) {

@@ -198,14 +198,18 @@ def mm(a: Tensor, b: Tensor, trans_a: bool = False, trans_b: bool = False,
         if relu:
             res = torch.relu(res)
         if mask is not None:
-            res = res * (mask.float() > 0)
+            # a select like the kernel's (and torch's ReLU backward): a NaN under mask <= 0 is 0
+            res = torch.where(mask.float() > 0, res, torch.zeros((), dtype=res.dtype))
         if out is None:
             out = torch.zeros(M if row_map is None else int(row_map.max()) + 1, N,
                               dtype=out_dtype) if row_map is not None else None
         if row_map is not None:
+            keep = row_map >= 0  # negative entries drop the row, as in the kernel's epilogue
+            rows = row_map.long()[keep]
+            res = res[keep]
             if beta != 0:
-                res = res + beta * out[row_map.long()].float()
-            out[row_map.long()] = res.to(out.dtype)
+                res = res + beta * out[rows].float()
+            out[rows] = res.to(out.dtype)
             return out
         if out is not None:
             if beta != 0:
@@ -473,11 +477,14 @@ def mm_grouped(problems, trans_a: bool = False, trans_b: bool = False,
         return
     if not probs[0]["a"].is_cuda:
         for q in probs:
-            if q.get("ncol"):
-                nc = int(q["ncol"])
-                q = dict(q, b=(q["b"][:nc] if trans_b else q["b"][:, :nc]))
+            nc = int(q.get("ncol") or 0)
+            if nc:
+                q = dict(q, b=(q["b"][:nc] if trans_b else q["b"][:, :nc]),
+                         bias=q["bias"][:nc] if q.get("bias") is not None else None)
             for out in (q["out"], q.get("out2")):
                 if out is not None:
+                    if nc:  # columns from ncol on (an output wider than ncol) are not stored
+                        out = out[:, :nc]
                     mm(q["a"], q["b"], trans_a=trans_a, trans_b=trans_b, out=out,
                        alpha=q.get("alpha", 1.0), beta=q.get("beta", 0.0), bias=q.get("bias"),
                        row_map=q.get("row_map"))

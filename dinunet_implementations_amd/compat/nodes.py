@@ -84,6 +84,11 @@ class LocalNode:
                 raise ValueError("lr_plateau_factor is implemented by the in-process runtime "
                                  "(runtime.site); the COINSTAC phase machines take warmup and "
                                  "decay only")
+            # the phase machines evaluate and checkpoint the raw weights
+            if float(c.get("ema_decay") or 0) > 0:
+                raise ValueError("ema_decay (the weight average) is implemented by the "
+                                 "in-process runtime (runtime.site); the COINSTAC phase machines "
+                                 "validate and test the raw weights")
             if c.get("lr_schedule") in ("linear", "cosine") and c.get("lr_decay_steps") is None:
                 raise ValueError(f"lr_schedule={c.get('lr_schedule')!r} needs an explicit "
                                  "lr_decay_steps in the COINSTAC phase machines")

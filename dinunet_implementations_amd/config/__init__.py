@@ -76,6 +76,12 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     "dsgd_bucket_mb": 4.0,
     # global-norm gradient clipping in the fused Adam (ops.FusedAdam max_grad_norm): 0 = off
     "max_grad_norm": 0,
+    # exponential moving average of the weights in the fused Adam (ops.FusedAdam ema_decay): 0 =
+    # off, else a decay in (0, 1); validation, checkpoint selection and test then score the
+    # average.  ema_warmup: the decay of update t is min(ema_decay, (1 + t) / (10 + t)).
+    # pretrain_args may override both.  Where ema_decay is unset (0), DINUNET_EMA_DECAY applies
+    "ema_decay": 0,
+    "ema_warmup": True,
     # learning-rate schedule in the fused Adam (ops.FusedAdam lr_schedule): None = off, or
     # "constant" / "linear" / "cosine" decay to lr_min at update lr_decay_steps (None: epochs x
     # updates per epoch of the phase that trains) after lr_warmup_steps updates of linear
@@ -347,6 +353,20 @@ def lr_schedule_of(cfg: Dict[str, Any]) -> Optional[Dict[str, Any]]:
             "decay_steps": None if T is None else int(T), "lr_min": float(cfg.get("lr_min") or 0.0)}
 
 
+def check_ema(cfg: Dict[str, Any]) -> None:
+    """The weight-averaging keys of ``cfg`` (normalised in place)."""
+    d = cfg.get("ema_decay")
+    d = 0 if d is None else d
+    if not _is_num(d) or not (d == 0 or 0 < d < 1):
+        raise ValueError(f"ema_decay must be 0 (off) or lie in (0, 1), got {d!r}")
+    cfg["ema_decay"] = d
+    w = cfg.get("ema_warmup")
+    w = True if w is None else w
+    if not isinstance(w, bool):
+        raise ValueError(f"ema_warmup must be true or false, got {w!r}")
+    cfg["ema_warmup"] = w
+
+
 def check_dp(cfg: Dict[str, Any]) -> None:
     """The private-release keys of ``cfg`` (normalised in place)."""
     for key in ("dp_clip_norm", "dp_noise_multiplier"):
@@ -386,6 +406,9 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if isinstance(mg, bool) or not isinstance(mg, (int, float)) or not (0 <= mg <= 3.4e38):
         raise ValueError(f"max_grad_norm must be a number >= 0 (0 = off), got {mg!r}")
     cfg["max_grad_norm"] = mg
+    check_ema(cfg)
+    if isinstance(cfg.get("pretrain_args"), dict):
+        check_ema({**cfg, **cfg["pretrain_args"]})
     check_lr_schedule(cfg)
     if isinstance(cfg.get("pretrain_args"), dict):  # the pretraining phase may override each key
         check_lr_schedule({**cfg, **cfg["pretrain_args"]})

@@ -96,6 +96,24 @@ step_prologue_kernel(StepPrologue sp) {
     prologue_item(sp, i, cur);
 }
 
+// a <-> b over n fp32 values (16-B aligned, distinct buffers): one pass, each thread holds both
+// float4s before it stores either; the n % 4 tail by workgroup 0
+__global__ void __launch_bounds__(256) swap_f32_kernel(float* a, float* b, long n) {
+  const long n4 = n >> 2;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4;
+       i += (long)gridDim.x * blockDim.x) {
+    const f32x4 x = reinterpret_cast<f32x4*>(a)[i], y = reinterpret_cast<f32x4*>(b)[i];
+    reinterpret_cast<f32x4*>(a)[i] = y;
+    reinterpret_cast<f32x4*>(b)[i] = x;
+  }
+  const long t = (n4 << 2) + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    const float x = a[t], y = b[t];
+    a[t] = y;
+    b[t] = x;
+  }
+}
+
 static int prologue_launch(const StepPrologue& sp, hipStream_t st) {
   const long total = sp.ux + sp.ug + sp.ny;
   if (total <= 0) return DN_OK;
@@ -133,6 +151,19 @@ DN_API int dn_step_gather(const void* gx, int gx_bf16, long row_elems, const lon
                                  ng, bump);
   if (rc != DN_OK) return rc;
   return prologue_launch(sp, st);
+}
+
+// Exchange two equal-length fp32 buffers (FusedAdam.swap_ema: the parameters and their average,
+// with no third buffer); twice restores both bit for bit.
+DN_API int dn_swap_f32(float* a, float* b, long n, hipStream_t st) {
+  if (n <= 0) return DN_OK;
+  if (!a || !b || a == b || (((uintptr_t)a | (uintptr_t)b) & 15)) return DN_BAD_SHAPE;
+  // (overlapping ranges would exchange nothing well-defined)
+  if ((a < b ? b - a : a - b) < n) return DN_BAD_SHAPE;
+  const long n4 = n / 4 + 1;
+  const long blocks = (n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048;
+  hipLaunchKernelGGL(swap_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a, b, n);
+  return dn_launch_status();
 }
 
 DN_API int dn_relu_bwd(const void* dy, const void* y, void* dym, long n, hipStream_t st) {

@@ -80,6 +80,27 @@ __device__ __forceinline__ float sched_lr(LrState* __restrict__ ls, int t) {
   return lr;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Exponential moving average of the parameters (FusedAdam ema_decay): e += (1 - d_t) (p - e) right
+// after the update, from the registers that hold the new p -- one more fp32 stream in and out of
+// the same launch.  The decay of update t (the number the bias corrections use) is
+//   d_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay
+// in double; 1 - d_t is rounded to fp32 once (FusedAdam.ema_decay_at is the host mirror).  A
+// skipped update and a priming launch neither read nor write e.  Workgroup 0 records d_t.
+struct EmaState {
+  float decay;    // host-written: the cap (FusedAdam.ema_decay)
+  int warmup;     // host-written: the (1 + t) / (10 + t) ramp on / off
+  float applied;  // kernel-written: the decay the last average used
+  int pad;
+};
+
+__device__ __forceinline__ float ema_omd(EmaState* __restrict__ es, int t) {
+  const double dec = (double)es->decay, td = (double)t;
+  const double d = es->warmup ? fmin(dec, (1.0 + td) / (10.0 + td)) : dec;
+  if (blockIdx.x == 0 && threadIdx.x == 0) es->applied = (float)d;
+  return (float)(1.0 - d);
+}
+
 // torch.optim.Adam semantics (L2 weight decay, no amsgrad):
 //   g += wd * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
@@ -87,13 +108,16 @@ __device__ __forceinline__ float sched_lr(LrState* __restrict__ ls, int t) {
 // CLIP: the gradient scale and the skip flag come from clip_coef (cs non-null).
 // SCHED: lr comes from sched_lr at this update's number (ls non-null; tdev null: tofs is the
 // host's step number); a skipped update still evaluates and records it.
-template <bool CLIP, bool SCHED>
+// EMA: the average ema follows the updated parameters (es non-null; the update number as for
+// SCHED).
+template <bool CLIP, bool SCHED, bool EMA>
 __global__ void __launch_bounds__(256)
 adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
             float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
             float bc1, float inv_sqrt_bc2, float grad_scale, const int* __restrict__ tdev,
             double b1d, double b2d, int tofs, long long* __restrict__ cursor,
-            ClipState* __restrict__ cs, LrState* __restrict__ ls) {
+            ClipState* __restrict__ cs, LrState* __restrict__ ls, float* __restrict__ ema,
+            EmaState* __restrict__ es) {
   // the device-fed batch cursor (prologue.h) advances once per update; no workgroup of this
   // launch reads it
   if (cursor && blockIdx.x == 0 && threadIdx.x == 0) *cursor += 1;
@@ -101,8 +125,10 @@ adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restric
   if constexpr (CLIP) {
     bool skip;
     grad_scale = clip_coef(cs, grad_scale, skip);
-    if (skip) return;  // p, m, v untouched; the step number still advances
+    if (skip) return;  // p, m, v (and the average) untouched; the step number still advances
   }
+  float omd = 0.f;
+  if constexpr (EMA) omd = ema_omd(es, tdev ? *tdev + tofs : tofs);
   if (tdev) {  // graph-replayable form: the step number lives on the device (adam_bump_kernel);
                // double math as on the host, so both forms round to the same fp32 corrections
     const double t = (double)(*tdev + tofs);  // tofs 0: the step prologue advanced it
@@ -126,6 +152,12 @@ adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restric
     reinterpret_cast<f32x4*>(p)[i] = pp;
     reinterpret_cast<f32x4*>(m)[i] = mm;
     reinterpret_cast<f32x4*>(v)[i] = vv;
+    if constexpr (EMA) {
+      f32x4 ee = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ee[e] = __builtin_fmaf(omd, pp[e] - ee[e], ee[e]);
+      reinterpret_cast<f32x4*>(ema)[i] = ee;
+    }
   }
   // scalar tail
   const long t = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -134,6 +166,7 @@ adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restric
     m[t] = b1 * m[t] + (1.f - b1) * gr;
     v[t] = b2 * v[t] + (1.f - b2) * gr * gr;
     p[t] -= step * m[t] / (sqrtf(v[t]) * inv_sqrt_bc2 + eps);
+    if constexpr (EMA) ema[t] = __builtin_fmaf(omd, p[t] - ema[t], ema[t]);
   }
 }
 
@@ -377,13 +410,14 @@ __global__ void __launch_bounds__(256) record_kernel(StepRecord r, int cofs) { r
 
 // SLAB: some segments take their gradient from split-K slabs (sl; slab_grad above).  Never with
 // CLIP: the norm needs the finished gradient before this launch.
-template <bool CLIP, bool SCHED, bool SLAB = false>
+template <bool CLIP, bool SCHED, bool EMA, bool SLAB = false>
 __global__ void __launch_bounds__(256)
 adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                  float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
                  float grad_scale, const int* __restrict__ tdev, double b1d, double b2d, int update,
                  int zero_grad, PackPlan pl, StepPrologue sp, int gofs, int ublocks, StepRecord rec,
-                 ClipState* __restrict__ cs, LrState* __restrict__ ls, SlabPlan sl) {
+                 ClipState* __restrict__ cs, LrState* __restrict__ ls, SlabPlan sl,
+                 float* __restrict__ ema, EmaState* __restrict__ es) {
   // the step's train record (rec.out set): the LAST workgroup; the cursor was advanced by this
   // step's encoder GEMM, so it names the batch this step trained on
   if (rec.out && blockIdx.x == gridDim.x - 1) {
@@ -413,6 +447,10 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
     const double t = (double)(*tdev);
     bc1 = (float)(1.0 - pow(b1d, t));
     inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(b2d, t)));
+  }
+  float omd = 0.f;
+  if constexpr (EMA) {  // (a priming launch and a skipped update leave the average alone)
+    if (update) omd = ema_omd(es, *tdev);
   }
   const float step = lr / bc1;
   const long n4 = n >> 2, stride = (long)ublocks * blockDim.x;
@@ -445,6 +483,12 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
       reinterpret_cast<f32x4*>(p)[i] = pp;
       reinterpret_cast<f32x4*>(m)[i] = mm;
       reinterpret_cast<f32x4*>(v)[i] = vv;
+      if constexpr (EMA) {
+        f32x4 ee = reinterpret_cast<f32x4*>(ema)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ee[e] = __builtin_fmaf(omd, pp[e] - ee[e], ee[e]);
+        reinterpret_cast<f32x4*>(ema)[i] = ee;
+      }
     }
     if (zero_grad) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (!SLAB) {
@@ -513,25 +557,39 @@ DN_API int dn_grad_sqnorm(const float* g, long n, void* clip, hipStream_t st) {
 }
 
 DN_API long dn_lr_state_size() { return (long)sizeof(LrState); }
+DN_API long dn_ema_state_size() { return (long)sizeof(EmaState); }
 
-// the <CLIP, SCHED> instantiation for a launch's clip / sched pointers (null = off)
-#define DN_ADAM_PICK(KERNEL, clip, sched)                        \
-  ((clip) ? ((sched) ? KERNEL<true, true> : KERNEL<true, false>) \
-          : ((sched) ? KERNEL<false, true> : KERNEL<false, false>))
+// the <CLIP, SCHED, EMA> instantiation for a launch's clip / sched / ema pointers (null = off)
+#define DN_ADAM_PICK_E(KERNEL, clip, sched, E)                         \
+  ((clip) ? ((sched) ? KERNEL<true, true, E> : KERNEL<true, false, E>) \
+          : ((sched) ? KERNEL<false, true, E> : KERNEL<false, false, E>))
+#define DN_ADAM_PICK(KERNEL, clip, sched, ema)                \
+  ((ema) ? DN_ADAM_PICK_E(KERNEL, clip, sched, true)          \
+         : DN_ADAM_PICK_E(KERNEL, clip, sched, false))
+
+// ema / ema_state: both null (off), or the average (16-byte aligned, as long as p) and its
+// EmaState
+static bool ema_args_ok(const float* ema, const void* es) {
+  if (!ema != !es) return false;
+  return !(((uintptr_t)ema & 15) || ((uintptr_t)es & 3));
+}
 
 // clip (a ClipState dn_grad_sqnorm filled for this gradient) non-null: the clipped update.
 // sched (an LrState) non-null: the scheduled rate at update number `step` (the host's count)
-// replaces lr.
+// replaces lr.  ema / ema_state non-null: the average follows, its decay that of update `step`.
 DN_API int dn_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1,
                    float b2, float eps, float wd, float bc1, float inv_sqrt_bc2, float grad_scale,
-                   long long* cursor, void* clip, int step, void* sched, hipStream_t st) {
+                   long long* cursor, void* clip, int step, void* sched, float* ema,
+                   void* ema_state, hipStream_t st) {
   if (n <= 0) return DN_OK;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
   if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched), dim3(grid_for(n / 4 + 1)),
+  if (!ema_args_ok(ema, ema_state)) return DN_BAD_SHAPE;
+  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched, ema), dim3(grid_for(n / 4 + 1)),
                      dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, inv_sqrt_bc2,
-                     grad_scale, (const int*)nullptr, 0.0, 0.0, sched ? step : 1, cursor,
-                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched));
+                     grad_scale, (const int*)nullptr, 0.0, 0.0, (sched || ema) ? step : 1, cursor,
+                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched), ema,
+                     reinterpret_cast<EmaState*>(ema_state));
   return dn_launch_status();
 }
 
@@ -539,14 +597,17 @@ DN_API int dn_adam(float* p, const float* g, float* m, float* v, long n, float l
 // HIP graph and replayed every step with the right bias corrections.  *tdev = completed steps.
 DN_API int dn_adam_dev(float* p, const float* g, float* m, float* v, long n, float lr, double b1,
                        double b2, float eps, float wd, float grad_scale, int* tdev, int prebumped,
-                       long long* cursor, void* clip, void* sched, hipStream_t st) {
+                       long long* cursor, void* clip, void* sched, float* ema, void* ema_state,
+                       hipStream_t st) {
   if (n <= 0) return DN_OK;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
   if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched), dim3(grid_for(n / 4 + 1)),
+  if (!ema_args_ok(ema, ema_state)) return DN_BAD_SHAPE;
+  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched, ema), dim3(grid_for(n / 4 + 1)),
                      dim3(256), 0, st, p, g, m, v, n, lr, (float)b1, (float)b2, eps, wd, 0.f, 0.f,
                      grad_scale, (const int*)tdev, b1, b2, prebumped ? 0 : 1, cursor,
-                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched));
+                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched), ema,
+                     reinterpret_cast<EmaState*>(ema_state));
   if (!prebumped) hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, tdev);
   return dn_launch_status();
 }
@@ -573,15 +634,18 @@ static bool slab_src_ok(const SlabSrc& r, const PackSeg& s, int Hd, int HD) {
 }
 
 // srcs: null, or cnt SlabSrc rows by segment (slab null: that segment reads g) -- only with an
-// unclipped update.
+// unclipped update.  ema / ema_state non-null: the average follows every update of this launch
+// (update = 0 leaves it alone).
 DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr, double b1,
                         double b2, float eps, float wd, float grad_scale, const int* tdev,
                         int update, int zero_grad, const void* segs, int cnt, int I, int Hd,
                         int HD, const void* gx, int gx_bf16, long row_elems, const long long* gy,
                         const long long* order, long nb, const long long* cursor, int B,
                         void* xb, long long* yd, long long* sd, int gofs, const void* record,
-                        void* clip, void* sched, const void* srcs, hipStream_t st) {
+                        void* clip, void* sched, const void* srcs, float* ema, void* ema_state,
+                        hipStream_t st) {
   if (n <= 0 || n % 4 || cnt < 0 || cnt > PACK_SEGS) return DN_BAD_SHAPE;
+  if (!ema_args_ok(ema, ema_state)) return DN_BAD_SHAPE;
   if (clip && !update) return DN_BAD_SHAPE;  // the partials belong to an update's gradient
   if (srcs && (clip || !update)) return DN_BAD_SHAPE;
   if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
@@ -630,12 +694,17 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
   // rest start as the first retire)
   auto parts = [](long items) { return (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096); };
   const int ub = parts(n / 4), gb = sp.gx ? parts(sp.ux + sp.ny) : 0;
-  auto kernel = DN_ADAM_PICK(adam_pack_kernel, clip, sched);
-  if (slabs) kernel = sched ? adam_pack_kernel<false, true, true> : adam_pack_kernel<false, false, true>;
+  auto kernel = DN_ADAM_PICK(adam_pack_kernel, clip, sched, ema);
+  if (slabs)
+    kernel = ema ? (sched ? adam_pack_kernel<false, true, true, true>
+                          : adam_pack_kernel<false, false, true, true>)
+                 : (sched ? adam_pack_kernel<false, true, false, true>
+                          : adam_pack_kernel<false, false, false, true>);
   hipLaunchKernelGGL(kernel, dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, p, g, m, v, n,
                      lr, (float)b1, (float)b2, eps, wd, grad_scale, tdev, b1, b2, update, zero_grad,
                      pl, sp, gofs, ub, rec, reinterpret_cast<ClipState*>(clip),
-                     reinterpret_cast<LrState*>(sched), sl);
+                     reinterpret_cast<LrState*>(sched), sl, ema,
+                     reinterpret_cast<EmaState*>(ema_state));
   return dn_launch_status();
 }
 

@@ -24,12 +24,12 @@ from . import _lib
 
 _lib.register("dn_adam", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
                           _lib.c_long] + [_lib.c_float] * 8 + [_lib.c_void_p] * 2
-              + [_lib.c_int] + [_lib.c_void_p] * 2)
+              + [_lib.c_int] + [_lib.c_void_p] * 4)
 _lib.register("dn_adam_dev", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
                               _lib.c_long, _lib.c_float, _lib.c_double, _lib.c_double,
                               _lib.c_float, _lib.c_float, _lib.c_float, _lib.c_void_p,
                               _lib.c_int, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
-                              _lib.c_void_p])
+                              _lib.c_void_p, _lib.c_void_p, _lib.c_void_p])
 _lib.register("dn_grad_sqnorm", [_lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_void_p])
 _lib.register("dn_step_gather", [_lib.c_void_p, _lib.c_int, _lib.c_long, _lib.c_void_p,
                                  _lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_int,
@@ -53,7 +53,9 @@ _lib.register("dn_adam_pack", [_lib.c_void_p] * 4 + [_lib.c_long, _lib.c_float, 
                                _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
                                _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
                                _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
-                               _lib.c_void_p, _lib.c_void_p, _lib.c_void_p])
+                               _lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
+                               _lib.c_void_p])
+_lib.register("dn_swap_f32", [_lib.c_void_p, _lib.c_void_p, _lib.c_long, _lib.c_void_p])
 _lib.register("dn_step_record", [_lib.c_void_p, _lib.c_int, _lib.c_void_p])
 
 
@@ -142,6 +144,19 @@ def _f32(x: float) -> float:
     return struct.unpack("f", struct.pack("f", float(x)))[0]
 
 
+# optim.hip EmaState: 4 four-byte words {fp32 decay, int32 warmup, fp32 applied, pad} (size
+# checked against the library on a GPU)
+_EMA_DECAY, _EMA_WARMUP, _EMA_APPLIED = range(3)
+EMA_WORDS = 4
+
+
+def _check_ema_decay(value) -> float:
+    d = float(value)
+    if not (d == 0.0 or (0.0 < d < 1.0 and _f32(d) < 1.0)):  # (an fp32 word on the device)
+        raise ValueError(f"ema_decay must be 0 (off) or a number in (0, 1), got {value!r}")
+    return d
+
+
 @dataclass
 class LrSchedule:
     """A learning rate as a function of the update number ``t`` (:meth:`FusedAdam.lr_at`):
@@ -211,11 +226,23 @@ class FusedAdam:
     run to ``DINUNET_LR_DECAY_STEPS``, default 10000), else off.  On / off is fixed here (it
     changes what is launched); ``lr``, ``lr_scale`` and the schedule's numbers live on the device,
     so they may change between replays of a captured graph.  ``constant`` with no warmup and
-    ``lr_scale`` 1 is bit-identical to the schedule being off."""
+    ``lr_scale`` 1 is bit-identical to the schedule being off.
+
+    ``ema_decay = d`` in (0, 1): ``ema``, an exponential moving average of the parameters
+    (``e_0 = p_0``), follows every update inside the same launch, ``e += (1 - d_t) (p - e)`` from
+    the registers that hold the new ``p``, with ``d_t`` = :meth:`ema_decay_at` of the update number
+    the bias corrections use (``ema_warmup``: ``min(d, (1 + t) / (10 + t))``), the same on every
+    step form; ``applied_ema_decay`` holds the decay the last average used.  A skipped update and
+    a priming launch leave ``ema`` alone (the skipped update still consumes its number).
+    :meth:`swap_ema` / :meth:`ema_weights` exchange parameters and average in place, which is how
+    an evaluation reads the average.  ``None``: the ``DINUNET_EMA_DECAY`` switch, else off; ``0``:
+    off.  On / off is fixed here (it changes what is launched); the decay lives on the device and
+    may change between replays of a captured graph."""
 
     def __init__(self, flat: FlatParams, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, max_grad_norm: Optional[float] = None,
-                 lr_schedule: Union[LrSchedule, Dict, str, None] = None):
+                 lr_schedule: Union[LrSchedule, Dict, str, None] = None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         self.flat = flat
         self._lrs: Optional[torch.Tensor] = None  # schedule state (optim.hip LrState)
         self._lr = float(lr)
@@ -268,6 +295,110 @@ class FusedAdam:
             self._lrs = torch.zeros(LR_WORDS, dtype=torch.int32, device=dev)
             self._lrs_f = self._lrs.view(torch.float32)
             self._write_lr_state()
+        if ema_decay is None:
+            env = os.environ.get("DINUNET_EMA_DECAY", "")
+            ema_decay = float(env) if env else 0.0
+        d = _check_ema_decay(ema_decay)
+        self.ema: Optional[torch.Tensor] = None  # the average (fp32, like flat.data)
+        self._emas: Optional[torch.Tensor] = None  # its device block (optim.hip EmaState)
+        self._ema_decay = d if d > 0 else None
+        self._ema_warmup = bool(ema_warmup)
+        self._swapped = False  # flat.data holds the average, ema the raw parameters
+        if d > 0:
+            dev = flat.data.device
+            if dev.type == "cuda":
+                L = _lib.lib()
+                L.dn_ema_state_size.restype = _lib.c_long
+                if int(L.dn_ema_state_size()) != EMA_WORDS * 4:
+                    raise RuntimeError("ema state layout mismatch with the kernel library")
+            self.ema = flat.data.detach().clone()
+            self._emas = torch.zeros(EMA_WORDS, dtype=torch.int32, device=dev)
+            self._emas_f = self._emas.view(torch.float32)
+            self._write_ema_state()
+
+    # weight average -----------------------------------------------------------------------------
+    def _write_ema_state(self):
+        """The host-written words of the device block (one small copy)."""
+        w = struct.pack("fi", self._ema_decay, int(self._ema_warmup))
+        self._emas[:_EMA_APPLIED].copy_(torch.tensor(struct.unpack("2i", w), dtype=torch.int32))
+
+    def _need_ema(self, what: str):
+        if self.ema is None:
+            raise ValueError(f"FusedAdam.{what}: the weight average is switched on or off when "
+                             "the optimizer is built (it changes what is launched)")
+
+    @property
+    def ema_decay(self) -> Optional[float]:
+        """The configured decay (None with the average off)."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value: Optional[float]):
+        on = value is not None and _check_ema_decay(value) > 0
+        if on != (self.ema is not None):
+            self._need_ema("ema_decay")
+            raise ValueError("FusedAdam.ema_decay: the weight average is switched on or off when "
+                             "the optimizer is built (it changes what is launched)")
+        if not on:
+            return
+        self._refuse_in_capture("ema_decay")
+        self._ema_decay = float(value)
+        self._write_ema_state()
+
+    @property
+    def ema_warmup(self) -> bool:
+        return self._ema_warmup
+
+    @property
+    def applied_ema_decay(self) -> Optional[torch.Tensor]:
+        """fp32 [] on the optimizer's device: the decay the last average used (None with the
+        average off)."""
+        return None if self._emas is None else self._emas_f[_EMA_APPLIED]
+
+    def ema_decay_at(self, t: int) -> float:
+        """The decay of update number ``t`` (1-based) as the kernels compute it (optim.hip
+        ema_omd), in double from the fp32 device word: ``min(d, (1 + t) / (10 + t))`` with the
+        warmup on, else ``d``.  The kernels multiply by ``fp32(1 - d_t)``."""
+        self._need_ema("ema_decay_at")
+        d, t = _f32(self._ema_decay), float(int(t))
+        return min(d, (1.0 + t) / (10.0 + t)) if self._ema_warmup else d
+
+    def swap_ema(self):
+        """Exchange the parameters and their average in place (``dn_swap_f32``, no third
+        buffer): after it the model computes with the average and ``ema`` holds the raw
+        parameters; twice restores both bit for bit.  No ``step*`` while swapped."""
+        self._need_ema("swap_ema")
+        if _capturing():
+            # the exchange would become a graph node that swaps again at every replay
+            raise RuntimeError("FusedAdam.swap_ema inside a HIP graph capture")
+        d = self.flat.data
+        if d.is_cuda:
+            _lib.call("dn_swap_f32", d.data_ptr(), self.ema.data_ptr(), d.numel(), _lib.stream())
+        else:
+            tmp = d.clone()
+            d.copy_(self.ema)
+            self.ema.copy_(tmp)
+        self._swapped = not self._swapped
+
+    def ema_weights(self):
+        """``with opt.ema_weights():`` -- the parameters are the average inside the scope and
+        are swapped back when it ends, however it ends."""
+        import contextlib
+        self._need_ema("ema_weights")
+
+        @contextlib.contextmanager
+        def scope():
+            self.swap_ema()
+            try:
+                yield self
+            finally:
+                self.swap_ema()
+        return scope()
+
+    def _refuse_swapped(self):
+        if self._swapped:
+            raise RuntimeError("FusedAdam: no update while the parameters are swapped with "
+                               "their average (swap_ema / ema_weights)")
 
     # learning-rate schedule ---------------------------------------------------------------------
     def _write_lr_state(self):
@@ -278,7 +409,7 @@ class FusedAdam:
         self._lrs[:_LR_APPLIED].copy_(torch.tensor(struct.unpack("6i", w), dtype=torch.int32))
 
     def _refuse_in_capture(self, what: str):
-        if self._lrs is not None and _capturing():
+        if (self._lrs is not None or self._emas is not None) and _capturing():
             # the write would become a graph node that resets the value at every replay
             raise RuntimeError(f"FusedAdam.{what} set inside a HIP graph capture")
 
@@ -422,6 +553,7 @@ class FusedAdam:
         self.flat.zero_grad()
 
     def step(self, grad_scale: float = 1.0):
+        self._refuse_swapped()
         self.step_count += 1
         b1, b2 = self.betas
         bc1 = 1 - b1 ** self.step_count
@@ -433,7 +565,7 @@ class FusedAdam:
                       self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
                       self.weight_decay, bc1, 1.0 / math.sqrt(bc2), grad_scale,
                       _lib.ptr(self.cursor), clip, self.step_count, _lib.ptr(self._lrs),
-                      _lib.stream())
+                      _lib.ptr(self.ema), _lib.ptr(self._emas), _lib.stream())
             return
         lr = self.lr_at(self.step_count)
         if self._lrs is not None:  # (recorded for a skipped update too: it consumed its number)
@@ -451,6 +583,10 @@ class FusedAdam:
         self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
         denom = (self.exp_avg_sq.sqrt() / math.sqrt(bc2)).add_(self.eps)
         d.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
+        if self.ema is not None:  # (not reached by a skipped update)
+            dt = self.ema_decay_at(self.step_count)
+            self._emas_f[_EMA_APPLIED] = dt
+            self.ema.add_((d - self.ema) * _f32(1.0 - dt))
 
     # HIP-graph form --------------------------------------------------------------------------
     def sync_device_step(self):
@@ -470,6 +606,7 @@ class FusedAdam:
         the counter in its step prologue instead (it passes :meth:`device_step` to the
         prologue launch before each replay), so the update is ONE graph node, not Adam + a
         one-thread bump kernel."""
+        self._refuse_swapped()
         d = self.flat.data
         if self._tdev is None:
             self.sync_device_step()
@@ -478,7 +615,8 @@ class FusedAdam:
         _lib.call("dn_adam_dev", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
                   self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
                   self.weight_decay, grad_scale, self._tdev.data_ptr(), int(prebumped),
-                  _lib.ptr(self.cursor), clip, _lib.ptr(self._lrs), _lib.stream())
+                  _lib.ptr(self.cursor), clip, _lib.ptr(self._lrs), _lib.ptr(self.ema),
+                  _lib.ptr(self._emas), _lib.stream())
 
     # Adam that also emits the next step's operands (optim.hip adam_pack_kernel) ------------------
     def attach_pack(self, pack, src=None, xb: Optional[torch.Tensor] = None,
@@ -565,6 +703,7 @@ class FusedAdam:
         ``cursor + gofs`` gathered.  ``update=False``: images + gather + zeroing only (priming).
         ``record``: a :meth:`StepRecorder.args` struct -- the step's score column and loss go to
         the recorder's rings at the cursor (one more workgroup of the same launch)."""
+        self._refuse_swapped()
         pack, tab, cnt, src, xb, yd, sd, copy_x = self._pack
         d = self.flat.data
         if self._tdev is None:
@@ -590,7 +729,7 @@ class FusedAdam:
                       int(update), 1, ctypes_addr(tab), cnt, pack.I, pack.Hd, pack.HD, *gx,
                       int(gofs), ctypes_addr(record) if (record is not None and update) else None,
                       clip, _lib.ptr(self._lrs), ctypes_addr(srcs) if srcs is not None else None,
-                      _lib.stream())
+                      _lib.ptr(self.ema), _lib.ptr(self._emas), _lib.stream())
         finally:
             self.drop_slabs()  # (the launch is in the stream: the slabs may be reused after it)
 
@@ -612,6 +751,13 @@ class FusedAdam:
             sd["lr_schedule"] = asdict(self._sched)
             sd["lr_scale"] = self._lr_scale
             sd["plateau_wait"] = int(self.plateau_wait)
+        if self.ema is not None:
+            if self._swapped:
+                raise RuntimeError("FusedAdam.state_dict while the parameters are swapped with "
+                                   "their average")
+            sd["ema"] = self.ema.detach().cpu()
+            sd["ema_decay"] = self._ema_decay
+            sd["ema_warmup"] = self._ema_warmup
         return sd
 
     def load_state_dict(self, sd: Dict):
@@ -634,6 +780,16 @@ class FusedAdam:
                 self.max_grad_norm = float(sd["max_grad_norm"])
             if "skipped" in sd:
                 self._clip_i[2] = int(sd["skipped"])
+        if self.ema is not None:  # (on / off stays as built)
+            self._refuse_swapped()
+            if "ema" in sd:
+                self.ema.copy_(sd["ema"].to(self.ema.device))
+                self._ema_warmup = bool(sd.get("ema_warmup", self._ema_warmup))
+                if sd.get("ema_decay"):
+                    self._ema_decay = _check_ema_decay(sd["ema_decay"])
+                self._write_ema_state()
+            else:  # an older checkpoint: the built values, the average restarts at the parameters
+                self.ema.copy_(self.flat.data)
 
 
 def step_prologue(x: torch.Tensor, xb: Optional[torch.Tensor], y: torch.Tensor,

@@ -153,6 +153,24 @@ def adam_(params, grads, exp_avg, exp_avg_sq, step: int, lr: float, beta1: float
     return params
 
 
+def ema_decay_at(t: int, decay: float, warmup: bool = True) -> float:
+    """The decay of the weight average at update ``t`` (1-based), in double, as optim.hip
+    ema_omd computes it: ``min(decay, (1 + t) / (10 + t))`` with the warmup on, else ``decay``,
+    ``decay`` being the fp32 device word."""
+    d = float(torch.tensor(float(decay), dtype=torch.float32))
+    t = float(int(t))
+    return min(d, (1.0 + t) / (10.0 + t)) if warmup else d
+
+
+def ema_update(e: Tensor, p: Tensor, t: int, decay: float, warmup: bool = True) -> Tensor:
+    """The weight average after update ``t`` in fp64: ``e + omd (p - e)`` with ``omd = 1 - d_t``
+    rounded to fp32 once (the word the kernels multiply by), from the average ``e`` before and
+    the updated parameters ``p``."""
+    omd = float(torch.tensor(1.0 - ema_decay_at(t, decay, warmup), dtype=torch.float32))
+    e64, p64 = e.detach().double(), p.detach().double()
+    return e64 + omd * (p64 - e64)
+
+
 # ---- differentially private gradient release (csrc/kernels/dp.hip) --------------------------------
 _PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 _PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85

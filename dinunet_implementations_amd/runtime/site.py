@@ -257,7 +257,12 @@ class FederatedSite:
     def _evaluate(self, trainer: NNTrainer, loader: DeviceLoader, cfg: Optional[Dict[str, Any]] = None,
                   logs: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         feed = self._eval_feed(trainer, loader, cfg if cfg is not None else self.cfg, logs)
-        return feed.run() if feed is not None else trainer.evaluate(loader)
+        # with the weight average on, every validation and test pass scores it: the parameters
+        # are the average inside the scope (both passes read the fp32 parameters in place --
+        # the feed repacks its operand images per pass, the host loop's stem packs in-stream,
+        # the head's evaluation forward takes the fp32 weights) and the raw weights after it
+        with trainer.ema_weights():
+            return feed.run() if feed is not None else trainer.evaluate(loader)
 
     def global_eval(self, trainer: NNTrainer, loader: DeviceLoader,
                     cfg: Optional[Dict[str, Any]] = None, logs: Optional[Dict[str, Any]] = None):
@@ -332,6 +337,9 @@ class FederatedSite:
                                  forward_loss=lambda m, x, y: trainer.forward_loss(x, y))
         opt = trainer.optimizer
         sched_on = getattr(opt, "applied_lr", None) is not None
+        ema_on = getattr(opt, "ema", None) is not None
+        if ema_on:
+            logs[f"{tag}ema_decay"] = opt.ema_decay
         plateau = float(cfg.get("lr_plateau_factor") or 0) if sched_on else 0.0
         if sched_on and not resume and cfg.get("lr_decay_steps") is None:
             # a fresh phase: the decay ends with its last update (a resumed one carries its own)
@@ -421,6 +429,8 @@ class FederatedSite:
                     int(trainer.optimizer.skipped_steps))
             if sched_on:  # the rate the epoch's last update used
                 logs.setdefault(f"{tag}learning_rate", []).append(float(opt.applied_lr))
+            if ema_on:  # the decay the epoch's last average used
+                logs.setdefault(f"{tag}ema_applied_decay", []).append(float(opt.applied_ema_decay))
             self._dp_log(engine, cfg, logs, tag)
             tl.append([round(avg.average, 6)] + met.get((monitor if monitor != "loss" else "auc",)))
             logs.setdefault(f"{tag}samples_per_sec", []).append(nsamp / dt if dt > 0 else 0.0)
@@ -572,9 +582,11 @@ class FederatedSite:
                 from ..parallel import DSGDEngine
                 from ..parallel.group import SiteGroup as _SG
                 solo = _SG(device=self.device)
-                if lr_schedule_of(pcfg) is not None or lr_schedule_of(self.cfg) is not None:
-                    # the phase's own schedule (pretrain_args may override each key; on / off
-                    # is fixed when the optimizer is built): nothing is trained yet
+                ema_of = lambda c: (float(c.get("ema_decay") or 0), c.get("ema_warmup", True))
+                if (lr_schedule_of(pcfg) is not None or lr_schedule_of(self.cfg) is not None
+                        or ema_of(pcfg) != ema_of(self.cfg)):
+                    # the phase's own schedule and weight average (pretrain_args may override each
+                    # key; on / off is fixed when the optimizer is built): nothing is trained yet
                     trainer._init_optimizer(
                         lr=float(pa.get("learning_rate", trainer.optimizer.lr)), cache=pcfg)
                 else:
@@ -586,6 +598,9 @@ class FederatedSite:
                 b = self._train_epochs(trainer, eng, data, pcfg, solo, fold_dir, seed, logs,
                                        tag="pretrain_")
                 trainer.load_checkpoint(os.path.join(fold_dir, "pretrain_checkpoint_best.pt"))
+                if getattr(trainer.optimizer, "ema", None) is not None:
+                    # what was validated is what is handed on: the averaged weights
+                    trainer.flat.data.copy_(trainer.optimizer.ema)
                 logs["pretrain_best_val_epoch"] = b["epoch"]
         elif self.group.rank == src:
             _PretrainSignal(self.group, fold_dir, self.cfg).done("1")
@@ -661,10 +676,17 @@ class FederatedSite:
             saved = last
         lo = None
         if saved is not None and os.path.exists(saved):
-            lo = torch.load(saved, map_location="cpu", weights_only=True).get("loss_options")
+            ck = torch.load(saved, map_location="cpu", weights_only=True)
+            lo = ck.get("loss_options")
             if lo:
                 cfg = dict(cfg, class_weights=list(lo["class_weights"]),
                            label_smoothing=lo["label_smoothing"])
+            od = (ck.get("optimizer") or {}).get("ema_decay")
+            if ck.get("ema") is not None and od:
+                # the checkpoint carries a weight average: it is scored (and continued) as such
+                cfg = dict(cfg, ema_decay=float(od),
+                           ema_warmup=bool(ck["optimizer"].get("ema_warmup", True)))
+            del ck
         trainer = self.Trainer(cache=cfg, state=self.state, device=self.device)
         trainer.init_nn(seed=int(cfg.get("seed", 0) or 0) + fold)  # same init on every site
         if cfg.get("class_weights") == "balanced":

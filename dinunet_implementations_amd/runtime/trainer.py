@@ -150,10 +150,13 @@ class NNTrainer:
         self.flat = FlatParams(self.parameters(), device=self.device["gpu"])
         lr = float(lr if lr is not None else cache.get("learning_rate", 1e-3))
         # (0 = off -> None, so the DINUNET_MAX_GRAD_NORM switch still applies; likewise an
-        # unset schedule and DINUNET_LR_SCHEDULE)
+        # unset schedule and DINUNET_LR_SCHEDULE, ema_decay and DINUNET_EMA_DECAY)
+        ew = cache.get("ema_warmup")
         self.optimizer = FusedAdam(self.flat, lr=lr, weight_decay=float(cache.get("weight_decay", 0.0)),
                                    max_grad_norm=float(cache.get("max_grad_norm") or 0) or None,
-                                   lr_schedule=lr_schedule_of(cache))
+                                   lr_schedule=lr_schedule_of(cache),
+                                   ema_decay=float(cache.get("ema_decay") or 0) or None,
+                                   ema_warmup=True if ew is None else bool(ew))
 
     def modules(self) -> nn.Module:
         """All registered modules as one container (engines walk ``.modules()``)."""
@@ -166,6 +169,16 @@ class NNTrainer:
     def eval(self):
         for m in self.nn.values():
             m.eval()
+
+    def ema_weights(self):
+        """The scope an evaluation runs in: the parameters are the optimizer's weight average
+        inside it (``FusedAdam.ema_weights``, swapped back when it ends); nothing with the
+        average off."""
+        opt = self.optimizer
+        if opt is not None and getattr(opt, "ema", None) is not None:
+            return opt.ema_weights()
+        import contextlib
+        return contextlib.nullcontext()
 
     @torch.no_grad()
     def evaluate(self, loader) -> Dict[str, Any]:
@@ -190,6 +203,11 @@ class NNTrainer:
         lo = self.loss_options()
         if lo is not None:  # beside the model section: a resume / test continues the objective
             st["loss_options"] = lo
+        ema = getattr(self.optimizer, "ema", None)
+        if ema is not None:
+            # the flat average beside the model section (which stays the raw weights under the
+            # reference's key names): what validation scored is what a test pass scores
+            st["ema"] = ema.detach().cpu()
         st.update(extra)
         return st
 
@@ -251,3 +269,11 @@ class NNTrainer:
         lo = st.get("loss_options")
         if lo and self.loss_options() is not None:
             self.set_loss_options(lo["class_weights"], lo["label_smoothing"])
+        ema = getattr(self.optimizer, "ema", None)
+        if ema is not None:
+            # the average as checkpointed, with or without the optimizer's state; a checkpoint
+            # that carries none restarts it at the loaded weights
+            if st.get("ema") is not None and st["ema"].numel() == ema.numel():
+                ema.copy_(st["ema"].to(ema.device))
+            elif not (load_optimizer and "ema" in (st.get("optimizer") or {})):
+                ema.copy_(self.flat.data)

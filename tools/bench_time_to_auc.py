@@ -46,6 +46,9 @@ def main():
     ap.add_argument("--compute-path", default="fused", choices=["fused", "reference"])
     ap.add_argument("--seed", type=int, default=0, help="model init / batch order")
     ap.add_argument("--full", action="store_true", help="run max-steps even after the target")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="weight average in the fused Adam (FusedAdam ema_decay); validation "
+                         "then scores the average.  Unset: the DINUNET_EMA_DECAY switch")
     a = ap.parse_args()
 
     from dinunet_implementations_amd.data.synthetic import ica_cohort_hard, ica_timecourses
@@ -78,15 +81,18 @@ def main():
                 m.use_fused = False
     flat = FlatParams(model.parameters())
     grp.broadcast(flat.data, 0)
-    opt = FusedAdam(flat, lr=a.lr)
+    opt = FusedAdam(flat, lr=a.lr, ema_decay=a.ema_decay)
     engine = make_engine(a.engine, model, flat, grp, {"precision_bits": "32", "seed": 0})
     step = TrainStep(model, flat, opt, engine, task="ica",
                      use_graph=dev.type == "cuda" and not ref_math)
     g = torch.Generator(device=dev).manual_seed(7 + grp.rank + 100 * a.seed)
 
     def global_auc():
+        import contextlib
         model.eval()
-        with torch.no_grad():
+        # with the weight average on, the validation scores it (swapped in for the pass)
+        scope = opt.ema_weights() if opt.ema is not None else contextlib.nullcontext()
+        with torch.no_grad(), scope:
             probs = []
             for i in range(0, len(Xva), 64):
                 out, _, _ = model.forward_loss(Xva[i:i + 64], Yva[i:i + 64])
@@ -136,6 +142,7 @@ def main():
                 a.cohort, a.signal,
                 ", label_noise=%g" % a.label_noise if a.cohort == "hard" else "")),
             "compute_path": a.compute_path,
+            "ema_decay": opt.ema_decay,
             "dtype": "fp32" if ref_math else "bf16",
             "curve": curve,
         }), flush=True)

@@ -105,11 +105,66 @@ __device__ __forceinline__ float ema_omd(EmaState* __restrict__ es, int t) {
 //   g += wd * p;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2
 //   p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
 // grad_scale folds the dSGD mean (1/world) or loss scaling into the same pass.
-// CLIP: the gradient scale and the skip flag come from clip_coef (cs non-null).
-// SCHED: lr comes from sched_lr at this update's number (ls non-null; tdev null: tofs is the
-// host's step number); a skipped update still evaluates and records it.
-// EMA: the average ema follows the updated parameters (es non-null; the update number as for
-// SCHED).
+//
+// what the element rule takes from the prologue of a launch
+struct AdamCoef {
+  float grad_scale, step, inv_sqrt_bc2, omd;  // step = lr / bc1, omd = 1 - d_t
+};
+
+// Prologue of every updating wave.  The update number is t = *tdev + tofs (tdev null: tofs is the
+// host's step number, and bc1 / inv_sqrt_bc2 are the host's corrections).  `update` clear on
+// entry is a priming launch (adam_pack_kernel): the recorded rate and decay are left alone.
+// CLIP: the gradient scale comes from clip_coef (cs non-null), and its skip clears `update`.
+// SCHED: lr comes from sched_lr at t (ls non-null); a skipped update still evaluates and records
+// it.
+// EMA: 1 - d_t of t (es non-null); a priming launch and a skipped update leave the average, and
+// its recorded decay, alone.
+template <bool CLIP, bool SCHED, bool EMA>
+__device__ __forceinline__ AdamCoef adam_begin(float lr, float bc1, float inv_sqrt_bc2,
+                                               float grad_scale, const int* __restrict__ tdev,
+                                               int tofs, double b1d, double b2d,
+                                               ClipState* __restrict__ cs, LrState* __restrict__ ls,
+                                               EmaState* __restrict__ es, int& update) {
+  const int t = tdev ? *tdev + tofs : tofs;
+  if constexpr (SCHED) {
+    if (update) lr = sched_lr(ls, t);
+  }
+  if constexpr (CLIP) {
+    bool skip;
+    grad_scale = clip_coef(cs, grad_scale, skip);
+    if (skip) update = 0;  // p, m, v (and the average) untouched
+  }
+  float omd = 0.f;
+  if (update) {
+    if constexpr (EMA) omd = ema_omd(es, t);
+    if (tdev) {  // graph-replayable forms: the step number lives on the device (adam_bump_kernel,
+                 // gemm.hip group_bump); double math as on the host, so every form rounds to the
+                 // same fp32 corrections
+      const double td = (double)t;
+      bc1 = (float)(1.0 - pow(b1d, td));
+      inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(b2d, td)));
+    }
+  }
+  return AdamCoef{grad_scale, lr / bc1, inv_sqrt_bc2, omd};
+}
+
+// The update of one element, and the average e after it from the register that holds the new p:
+// the one place the rule is written, for adam_kernel's float4 loop and scalar tail and for
+// adam_pack_kernel's loop, so the step forms agree bit for bit by construction.  The float4 loads
+// and stores around it stay in the kernels: moved into a function of their own (by reference or
+// by value), the compiler orders the two products of gr the other way round and contracts the
+// other one into the sum, which moves m and v by an ulp (tests/test_adam_bits_gpu.py).
+template <bool EMA>
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float& e,
+                                          float grad_scale, float wd, float b1, float b2,
+                                          float step, float inv_sqrt_bc2, float eps, float omd) {
+  const float gr = g * grad_scale + wd * p;
+  m = b1 * m + (1.f - b1) * gr;
+  v = b2 * v + (1.f - b2) * gr * gr;
+  p -= step * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
+  if constexpr (EMA) e = __builtin_fmaf(omd, p - e, e);
+}
+
 template <bool CLIP, bool SCHED, bool EMA>
 __global__ void __launch_bounds__(256)
 adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -121,55 +176,38 @@ adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restric
   // the device-fed batch cursor (prologue.h) advances once per update; no workgroup of this
   // launch reads it
   if (cursor && blockIdx.x == 0 && threadIdx.x == 0) *cursor += 1;
-  if constexpr (SCHED) lr = sched_lr(ls, tdev ? *tdev + tofs : tofs);
-  if constexpr (CLIP) {
-    bool skip;
-    grad_scale = clip_coef(cs, grad_scale, skip);
-    if (skip) return;  // p, m, v (and the average) untouched; the step number still advances
-  }
-  float omd = 0.f;
-  if constexpr (EMA) omd = ema_omd(es, tdev ? *tdev + tofs : tofs);
-  if (tdev) {  // graph-replayable form: the step number lives on the device (adam_bump_kernel);
-               // double math as on the host, so both forms round to the same fp32 corrections
-    const double t = (double)(*tdev + tofs);  // tofs 0: the step prologue advanced it
-    bc1 = (float)(1.0 - pow(b1d, t));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(b2d, t)));
-  }
+  int update = 1;
+  const AdamCoef c = adam_begin<CLIP, SCHED, EMA>(lr, bc1, inv_sqrt_bc2, grad_scale, tdev, tofs, b1d,
+                                                  b2d, cs, ls, es, update);
+  if (!update) return;  // skipped: the step number still advances
   const long n4 = n >> 2;
-  const float step = lr / bc1;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
     f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
     f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
     f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+    f32x4 ee = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (EMA) ee = reinterpret_cast<f32x4*>(ema)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float gr = gg[e] * grad_scale + wd * pp[e];
-      mm[e] = b1 * mm[e] + (1.f - b1) * gr;
-      vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
-      pp[e] -= step * mm[e] / (sqrtf(vv[e]) * inv_sqrt_bc2 + eps);
+      float p_ = pp[e], m_ = mm[e], v_ = vv[e], e_ = ee[e];
+      adam_elem<EMA>(p_, gg[e], m_, v_, e_, c.grad_scale, wd, b1, b2, c.step, c.inv_sqrt_bc2, eps,
+                     c.omd);
+      pp[e] = p_, mm[e] = m_, vv[e] = v_, ee[e] = e_;
     }
     reinterpret_cast<f32x4*>(p)[i] = pp;
     reinterpret_cast<f32x4*>(m)[i] = mm;
     reinterpret_cast<f32x4*>(v)[i] = vv;
-    if constexpr (EMA) {
-      f32x4 ee = reinterpret_cast<f32x4*>(ema)[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ee[e] = __builtin_fmaf(omd, pp[e] - ee[e], ee[e]);
-      reinterpret_cast<f32x4*>(ema)[i] = ee;
-    }
+    if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ee;
   }
   // scalar tail
   const long t = (n4 << 2) + blockIdx.x * (long)blockDim.x + threadIdx.x;
   if (blockIdx.x == 0 && t < n) {
-    float gr = g[t] * grad_scale + wd * p[t];
-    m[t] = b1 * m[t] + (1.f - b1) * gr;
-    v[t] = b2 * v[t] + (1.f - b2) * gr * gr;
-    p[t] -= step * m[t] / (sqrtf(v[t]) * inv_sqrt_bc2 + eps);
-    if constexpr (EMA) ema[t] = __builtin_fmaf(omd, p[t] - ema[t], ema[t]);
+    float none = 0.f;
+    adam_elem<EMA>(p[t], g[t], m[t], v[t], EMA ? ema[t] : none, c.grad_scale, wd, b1, b2, c.step,
+                   c.inv_sqrt_bc2, eps, c.omd);
   }
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // Fused Adam that also emits the NEXT step's operands: every updated
@@ -434,25 +472,11 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
       prologue_item(sp, i, c);  // sp.ug == 0: the zeroing rides in the update below
     return;
   }
-  if constexpr (SCHED) {  // (priming launches, update = 0, leave the recorded rate alone)
-    if (update) lr = sched_lr(ls, *tdev);
-  }
-  if constexpr (CLIP) {  // (launched with update set only)
-    bool skip;
-    grad_scale = clip_coef(cs, grad_scale, skip);
-    if (skip) update = 0;  // images from the unchanged parameters, gradient still zeroed
-  }
-  float bc1 = 1.f, inv_sqrt_bc2 = 1.f;
-  if (update) {  // the encoder GEMM of this step advanced *tdev (prebumped form)
-    const double t = (double)(*tdev);
-    bc1 = (float)(1.0 - pow(b1d, t));
-    inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(b2d, t)));
-  }
-  float omd = 0.f;
-  if constexpr (EMA) {  // (a priming launch and a skipped update leave the average alone)
-    if (update) omd = ema_omd(es, *tdev);
-  }
-  const float step = lr / bc1;
+  // the encoder GEMM of this step advanced *tdev (prebumped form: tofs 0); CLIP is launched with
+  // update set only, and a skip clears it: images from the unchanged parameters, gradient still
+  // zeroed
+  const AdamCoef c = adam_begin<CLIP, SCHED, EMA>(lr, 1.f, 1.f, grad_scale, tdev, 0, b1d, b2d, cs, ls,
+                                                  es, update);
   const long n4 = n >> 2, stride = (long)ublocks * blockDim.x;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += stride) {
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
@@ -473,22 +497,19 @@ adam_pack_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict
       }
       f32x4 mm = reinterpret_cast<f32x4*>(m)[i];
       f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+      f32x4 ee = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (EMA) ee = reinterpret_cast<f32x4*>(ema)[i];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float gr = gg[e] * grad_scale + wd * pp[e];
-        mm[e] = b1 * mm[e] + (1.f - b1) * gr;
-        vv[e] = b2 * vv[e] + (1.f - b2) * gr * gr;
-        pp[e] -= step * mm[e] / (sqrtf(vv[e]) * inv_sqrt_bc2 + eps);
+        float p_ = pp[e], m_ = mm[e], v_ = vv[e], e_ = ee[e];
+        adam_elem<EMA>(p_, gg[e], m_, v_, e_, c.grad_scale, wd, b1, b2, c.step, c.inv_sqrt_bc2,
+                       eps, c.omd);
+        pp[e] = p_, mm[e] = m_, vv[e] = v_, ee[e] = e_;
       }
       reinterpret_cast<f32x4*>(p)[i] = pp;
       reinterpret_cast<f32x4*>(m)[i] = mm;
       reinterpret_cast<f32x4*>(v)[i] = vv;
-      if constexpr (EMA) {
-        f32x4 ee = reinterpret_cast<f32x4*>(ema)[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ee[e] = __builtin_fmaf(omd, pp[e] - ee[e], ee[e]);
-        reinterpret_cast<f32x4*>(ema)[i] = ee;
-      }
+      if constexpr (EMA) reinterpret_cast<f32x4*>(ema)[i] = ee;
     }
     if (zero_grad) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (!SLAB) {
@@ -559,56 +580,69 @@ DN_API int dn_grad_sqnorm(const float* g, long n, void* clip, hipStream_t st) {
 DN_API long dn_lr_state_size() { return (long)sizeof(LrState); }
 DN_API long dn_ema_state_size() { return (long)sizeof(EmaState); }
 
-// the <CLIP, SCHED, EMA> instantiation for a launch's clip / sched / ema pointers (null = off)
-#define DN_ADAM_PICK_E(KERNEL, clip, sched, E)                         \
-  ((clip) ? ((sched) ? KERNEL<true, true, E> : KERNEL<true, false, E>) \
-          : ((sched) ? KERNEL<false, true, E> : KERNEL<false, false, E>))
-#define DN_ADAM_PICK(KERNEL, clip, sched, ema)                \
-  ((ema) ? DN_ADAM_PICK_E(KERNEL, clip, sched, true)          \
-         : DN_ADAM_PICK_E(KERNEL, clip, sched, false))
+// The argument block of every Adam launcher (ops/optim.py _AdamArgs is the host mirror), by
+// address across the C ABI; the launchers hand its fields to the kernels.
+struct AdamArgs {
+  float *p, *g, *m, *v;
+  float* ema;  // the average (null: off; with es)
+  long n;
+  float lr, b1, b2, eps, wd, grad_scale;
+  float bc1, inv_sqrt_bc2;  // the host's bias corrections (tdev null)
+  double b1d, b2d;          // the betas as the host holds them (tdev non-null)
+  int* tdev;                // device step counter, null: tofs is the host's step number
+  int tofs, pad;            // this update's number is *tdev + tofs
+  long long* cursor;        // adam_kernel: the device-fed batch cursor to advance (null: none)
+  ClipState* cs;            // non-null: the clipped update (CLIP)
+  LrState* ls;              // non-null: the scheduled rate (SCHED)
+  EmaState* es;             // non-null: the average follows (EMA)
+};
+static_assert(sizeof(AdamArgs) == 144, "ops/optim.py _AdamArgs mirrors this layout");
 
-// ema / ema_state: both null (off), or the average (16-byte aligned, as long as p) and its
-// EmaState
-static bool ema_args_ok(const float* ema, const void* es) {
-  if (!ema != !es) return false;
-  return !(((uintptr_t)ema & 15) || ((uintptr_t)es & 3));
+// The instantiations by flag bits, 1 CLIP | 2 SCHED | 4 EMA (| 8 SLAB): the state pointers of a
+// launch (null = off) pick one.  There is no CLIP with SLAB (refused on the host).
+using AdamKernel = decltype(&adam_kernel<false, false, false>);
+using AdamPackKernel = decltype(&adam_pack_kernel<false, false, false>);
+static constexpr AdamKernel ADAM_KERNELS[8] = {
+    adam_kernel<false, false, false>, adam_kernel<true, false, false>,
+    adam_kernel<false, true, false>,  adam_kernel<true, true, false>,
+    adam_kernel<false, false, true>,  adam_kernel<true, false, true>,
+    adam_kernel<false, true, true>,   adam_kernel<true, true, true>};
+static constexpr AdamPackKernel ADAM_PACK_KERNELS[16] = {
+    adam_pack_kernel<false, false, false>,       adam_pack_kernel<true, false, false>,
+    adam_pack_kernel<false, true, false>,        adam_pack_kernel<true, true, false>,
+    adam_pack_kernel<false, false, true>,        adam_pack_kernel<true, false, true>,
+    adam_pack_kernel<false, true, true>,         adam_pack_kernel<true, true, true>,
+    adam_pack_kernel<false, false, false, true>, nullptr,
+    adam_pack_kernel<false, true, false, true>,  nullptr,
+    adam_pack_kernel<false, false, true, true>,  nullptr,
+    adam_pack_kernel<false, true, true, true>,   nullptr};
+static int adam_flags(const AdamArgs& a) { return (a.cs ? 1 : 0) | (a.ls ? 2 : 0) | (a.es ? 4 : 0); }
+
+// What every Adam launch requires of its block: p, g, m, v and the average 16-byte aligned, the
+// state blocks word aligned, and ema / es both null (off) or both set (the average is as long as
+// p).  cs is a ClipState dn_grad_sqnorm filled for this gradient.
+DN_API long dn_adam_args_size() { return (long)sizeof(AdamArgs); }
+static bool adam_args_ok(const AdamArgs& a) {
+  if (((uintptr_t)a.p | (uintptr_t)a.g | (uintptr_t)a.m | (uintptr_t)a.v | (uintptr_t)a.ema) & 15)
+    return false;
+  if (((uintptr_t)a.ls | (uintptr_t)a.es) & 3) return false;
+  return !a.ema == !a.es;
 }
 
-// clip (a ClipState dn_grad_sqnorm filled for this gradient) non-null: the clipped update.
-// sched (an LrState) non-null: the scheduled rate at update number `step` (the host's count)
-// replaces lr.  ema / ema_state non-null: the average follows, its decay that of update `step`.
-DN_API int dn_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1,
-                   float b2, float eps, float wd, float bc1, float inv_sqrt_bc2, float grad_scale,
-                   long long* cursor, void* clip, int step, void* sched, float* ema,
-                   void* ema_state, hipStream_t st) {
-  if (n <= 0) return DN_OK;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
-  if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
-  if (!ema_args_ok(ema, ema_state)) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched, ema), dim3(grid_for(n / 4 + 1)),
-                     dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, inv_sqrt_bc2,
-                     grad_scale, (const int*)nullptr, 0.0, 0.0, (sched || ema) ? step : 1, cursor,
-                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched), ema,
-                     reinterpret_cast<EmaState*>(ema_state));
-  return dn_launch_status();
-}
-
-// Adam whose step number t is read from (and then advanced in) device memory: capturable in a
-// HIP graph and replayed every step with the right bias corrections.  *tdev = completed steps.
-DN_API int dn_adam_dev(float* p, const float* g, float* m, float* v, long n, float lr, double b1,
-                       double b2, float eps, float wd, float grad_scale, int* tdev, int prebumped,
-                       long long* cursor, void* clip, void* sched, float* ema, void* ema_state,
-                       hipStream_t st) {
-  if (n <= 0) return DN_OK;
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
-  if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
-  if (!ema_args_ok(ema, ema_state)) return DN_BAD_SHAPE;
-  hipLaunchKernelGGL(DN_ADAM_PICK(adam_kernel, clip, sched, ema), dim3(grid_for(n / 4 + 1)),
-                     dim3(256), 0, st, p, g, m, v, n, lr, (float)b1, (float)b2, eps, wd, 0.f, 0.f,
-                     grad_scale, (const int*)tdev, b1, b2, prebumped ? 0 : 1, cursor,
-                     reinterpret_cast<ClipState*>(clip), reinterpret_cast<LrState*>(sched), ema,
-                     reinterpret_cast<EmaState*>(ema_state));
-  if (!prebumped) hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, tdev);
+// One adam_kernel launch.  tdev null: update number tofs and the bias corrections come from the
+// host.  tdev non-null: the number is *tdev + tofs (*tdev = completed steps), so the launch is
+// capturable in a HIP graph and replayed every step with the right bias corrections; `bump`: the
+// one-thread launch that advances *tdev follows (tofs 1), else the caller's step prologue
+// advanced it already (tofs 0).
+DN_API int dn_adam(const AdamArgs* args, int bump, hipStream_t st) {
+  if (!args || (bump && !args->tdev)) return DN_BAD_SHAPE;
+  const AdamArgs& a = *args;
+  if (a.n <= 0) return DN_OK;
+  if (!adam_args_ok(a)) return DN_BAD_SHAPE;
+  hipLaunchKernelGGL(ADAM_KERNELS[adam_flags(a)], dim3(grid_for(a.n / 4 + 1)), dim3(256), 0, st,
+                     a.p, a.g, a.m, a.v, a.n, a.lr, a.b1, a.b2, a.eps, a.wd, a.bc1, a.inv_sqrt_bc2,
+                     a.grad_scale, a.tdev, a.b1d, a.b2d, a.tofs, a.cursor, a.cs, a.ls, a.ema, a.es);
+  if (bump) hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, a.tdev);
   return dn_launch_status();
 }
 
@@ -633,31 +667,32 @@ static bool slab_src_ok(const SlabSrc& r, const PackSeg& s, int Hd, int HD) {
   return s.n == rows;
 }
 
-// srcs: null, or cnt SlabSrc rows by segment (slab null: that segment reads g) -- only with an
-// unclipped update.  ema / ema_state non-null: the average follows every update of this launch
-// (update = 0 leaves it alone).
-DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr, double b1,
-                        double b2, float eps, float wd, float grad_scale, const int* tdev,
-                        int update, int zero_grad, const void* segs, int cnt, int I, int Hd,
-                        int HD, const void* gx, int gx_bf16, long row_elems, const long long* gy,
-                        const long long* order, long nb, const long long* cursor, int B,
-                        void* xb, long long* yd, long long* sd, int gofs, const void* record,
-                        void* clip, void* sched, const void* srcs, float* ema, void* ema_state,
-                        hipStream_t st) {
+static bool record_ok(const StepRecord& r) {
+  return r.out && r.loss && r.rs && r.rl && r.cursor && r.n > 0 && r.B > 0 &&
+         (r.col < 0 ? r.pred != nullptr : r.ld > r.col);
+}
+
+// args: the update's block (tofs 0: the step's encoder GEMM advanced *tdev; update = 0 leaves the
+// average alone).  srcs: null, or cnt SlabSrc rows by segment (slab null: that segment reads g)
+// -- only with an unclipped update.
+DN_API int dn_adam_pack(const AdamArgs* args, int update, int zero_grad, const void* segs, int cnt,
+                        int I, int Hd, int HD, const void* gx, int gx_bf16, long row_elems,
+                        const long long* gy, const long long* order, long nb,
+                        const long long* cursor, int B, void* xb, long long* yd, long long* sd,
+                        int gofs, const void* record, const void* srcs, hipStream_t st) {
+  if (!args) return DN_BAD_SHAPE;
+  const AdamArgs& a = *args;
+  const long n = a.n;
   if (n <= 0 || n % 4 || cnt < 0 || cnt > PACK_SEGS) return DN_BAD_SHAPE;
-  if (!ema_args_ok(ema, ema_state)) return DN_BAD_SHAPE;
-  if (clip && !update) return DN_BAD_SHAPE;  // the partials belong to an update's gradient
-  if (srcs && (clip || !update)) return DN_BAD_SHAPE;
-  if ((uintptr_t)sched & 3) return DN_BAD_SHAPE;
+  if (!adam_args_ok(a)) return DN_BAD_SHAPE;
+  if (a.cs && !update) return DN_BAD_SHAPE;  // the partials belong to an update's gradient
+  if (srcs && (a.cs || !update)) return DN_BAD_SHAPE;
   StepRecord rec{};
   if (record && update) {
     rec = *reinterpret_cast<const StepRecord*>(record);
-    if (!rec.out || !rec.loss || !rec.rs || !rec.rl || !rec.cursor || rec.n <= 0 || rec.B <= 0 ||
-        (rec.col < 0 ? !rec.pred : rec.ld <= rec.col))
-      return DN_BAD_SHAPE;
+    if (!record_ok(rec)) return DN_BAD_SHAPE;
   }
-  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return DN_BAD_SHAPE;
-  if (update && !tdev) return DN_BAD_SHAPE;
+  if (update && !a.tdev) return DN_BAD_SHAPE;
   PackPlan pl{};
   pl.cnt = cnt;
   pl.I = I;
@@ -687,24 +722,19 @@ DN_API int dn_adam_pack(float* p, float* g, float* m, float* v, long n, float lr
   StepPrologue sp{};
   if (gx) {
     const int rc = prologue_gather(sp, gx, gx_bf16, row_elems, gy, order, nb, cursor, B, xb, yd,
-                                   g, 0, nullptr, sd);
+                                   a.g, 0, nullptr, sd);
     if (rc != DN_OK) return rc;
   }
   // one item per thread up to 4096 workgroups per part (the chip holds ~2048 at a time; the
   // rest start as the first retire)
   auto parts = [](long items) { return (int)((items + 255) / 256 < 4096 ? (items + 255) / 256 : 4096); };
   const int ub = parts(n / 4), gb = sp.gx ? parts(sp.ux + sp.ny) : 0;
-  auto kernel = DN_ADAM_PICK(adam_pack_kernel, clip, sched, ema);
-  if (slabs)
-    kernel = ema ? (sched ? adam_pack_kernel<false, true, true, true>
-                          : adam_pack_kernel<false, false, true, true>)
-                 : (sched ? adam_pack_kernel<false, true, false, true>
-                          : adam_pack_kernel<false, false, false, true>);
-  hipLaunchKernelGGL(kernel, dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, p, g, m, v, n,
-                     lr, (float)b1, (float)b2, eps, wd, grad_scale, tdev, b1, b2, update, zero_grad,
-                     pl, sp, gofs, ub, rec, reinterpret_cast<ClipState*>(clip),
-                     reinterpret_cast<LrState*>(sched), sl, ema,
-                     reinterpret_cast<EmaState*>(ema_state));
+  const AdamPackKernel kernel = ADAM_PACK_KERNELS[adam_flags(a) | (slabs ? 8 : 0)];
+  if (!kernel) return DN_BAD_SHAPE;  // (CLIP with SLAB: refused above already)
+  hipLaunchKernelGGL(kernel,
+                     dim3(ub + gb + (rec.out ? 1 : 0)), dim3(256), 0, st, a.p, a.g, a.m, a.v, n,
+                     a.lr, a.b1, a.b2, a.eps, a.wd, a.grad_scale, a.tdev, a.b1d, a.b2d, update,
+                     zero_grad, pl, sp, gofs, ub, rec, a.cs, a.ls, sl, a.ema, a.es);
   return dn_launch_status();
 }
 
@@ -714,9 +744,7 @@ DN_API long dn_step_record_size() { return (long)sizeof(StepRecord); }
 DN_API int dn_step_record(const void* record, int cofs, hipStream_t st) {
   if (!record) return DN_BAD_SHAPE;
   const StepRecord r = *reinterpret_cast<const StepRecord*>(record);
-  if (!r.out || !r.loss || !r.rs || !r.rl || !r.cursor || r.n <= 0 || r.B <= 0 ||
-      (r.col < 0 ? !r.pred : r.ld <= r.col))
-    return DN_BAD_SHAPE;
+  if (!record_ok(r)) return DN_BAD_SHAPE;
   hipLaunchKernelGGL(record_kernel, dim3(1), dim3(256), 0, st, r, cofs);
   return dn_launch_status();
 }

@@ -98,6 +98,25 @@ def lib() -> ctypes.CDLL:
     return L
 
 
+_CHECKED: dict = {}  # size symbol -> the layout that passed
+
+
+def checked_struct(layout, size_symbol: str, what: str, **counts):
+    """``layout`` -- a ``ctypes.Structure`` type, or the byte count of a block kept as tensor
+    words -- against the library's ``size_symbol()``, and every ``symbol=value`` of ``counts``
+    against the library's ``symbol()``; returns ``layout``.  A layout that passed is not asked
+    again (the per-step argument blocks come through here)."""
+    if _CHECKED.get(size_symbol) == layout:
+        return layout
+    size_of = getattr(lib(), size_symbol)
+    size_of.restype = c_long
+    size = layout if isinstance(layout, int) else ctypes.sizeof(layout)
+    if int(size_of()) != size or any(int(getattr(lib(), k)()) != v for k, v in counts.items()):
+        raise RuntimeError(f"{what} layout mismatch with the kernel library")
+    _CHECKED[size_symbol] = layout
+    return layout
+
+
 def require_native() -> bool:
     return os.environ.get("DINUNET_REQUIRE_NATIVE", "1") != "0"
 

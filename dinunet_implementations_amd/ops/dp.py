@@ -80,11 +80,8 @@ class DPState:
         if not (0 <= stream < 2 ** 32):
             raise ValueError(f"stream must be an integer in [0, 2^32), got {stream!r}")
         if self.device.type == "cuda":
-            L = _lib.lib()
-            L.dn_dp_state_size.restype = _lib.c_long
-            if (int(L.dn_dp_parts()) != DP_PARTS
-                    or int(L.dn_dp_state_size()) != DP_PARTS * 8 + DP_WORDS * 4):
-                raise RuntimeError("dp state layout mismatch with the kernel library")
+            _lib.checked_struct(DP_PARTS * 8 + DP_WORDS * 4, "dn_dp_state_size", "dp state",
+                                dn_dp_parts=DP_PARTS)
         self._clip_norm, self._sigma, self.seed, self.stream = c, s, seed, stream
         self._block = torch.zeros(DP_PARTS + DP_WORDS // 2, dtype=torch.float64, device=self.device)
         self._f = self._block[DP_PARTS:].view(torch.float32)

@@ -32,11 +32,7 @@ def _boundary_type():
                         ("loss_b", P), ("cursor", P), ("ticket", P), ("gx", P), ("gy", P),
                         ("xb", P), ("yd", P), ("N", L), ("nb", L), ("ld", L), ("C", I),
                         ("n_prev", I), ("cap", I), ("f8", I), ("mode", I)]
-        lib = _lib.lib()
-        lib.dn_eval_boundary_size.restype = ctypes.c_long
-        if ctypes.sizeof(_Eb) != lib.dn_eval_boundary_size():
-            raise RuntimeError("evaluation boundary layout mismatch with the kernel library")
-        _BOUNDARY = _Eb
+        _BOUNDARY = _lib.checked_struct(_Eb, "dn_eval_boundary_size", "evaluation boundary")
     return _BOUNDARY
 
 

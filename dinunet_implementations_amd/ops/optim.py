@@ -11,6 +11,7 @@ Semantics match ``torch.optim.Adam`` / ``torch.optim.SGD`` (checked against them
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 import struct
@@ -22,19 +23,13 @@ import torch.nn as nn
 
 from . import _lib
 
-_lib.register("dn_adam", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
-                          _lib.c_long] + [_lib.c_float] * 8 + [_lib.c_void_p] * 2
-              + [_lib.c_int] + [_lib.c_void_p] * 4)
-_lib.register("dn_adam_dev", [_lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
-                              _lib.c_long, _lib.c_float, _lib.c_double, _lib.c_double,
-                              _lib.c_float, _lib.c_float, _lib.c_float, _lib.c_void_p,
-                              _lib.c_int, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
-                              _lib.c_void_p, _lib.c_void_p, _lib.c_void_p])
+_P, _I, _L, _F, _D = _lib.c_void_p, _lib.c_int, _lib.c_long, _lib.c_float, _lib.c_double
+# the device-feed arguments X ... B of the gathering launchers (DeviceSource.feed_args)
+_FEED = [_P, _I, _L, _P, _P, _L, _P, _I]
+
+_lib.register("dn_adam", [_P, _I, _P])  # (block, bump, stream)
 _lib.register("dn_grad_sqnorm", [_lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_void_p])
-_lib.register("dn_step_gather", [_lib.c_void_p, _lib.c_int, _lib.c_long, _lib.c_void_p,
-                                 _lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_int,
-                                 _lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
-                                 _lib.c_void_p, _lib.c_void_p])
+_lib.register("dn_step_gather", _FEED + [_P, _P, _P, _L, _P, _P])
 _lib.register("dn_step_prologue", [_lib.c_void_p, _lib.c_long, _lib.c_void_p, _lib.c_void_p,
                                    _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
                                    _lib.c_void_p, _lib.c_void_p])
@@ -46,22 +41,36 @@ _lib.register("dn_cast_f32_bf16", [_lib.c_void_p, _lib.c_void_p, _lib.c_long, _l
 _lib.register("dn_cast_bf16_f32", [_lib.c_void_p, _lib.c_void_p, _lib.c_long, _lib.c_float,
                                    _lib.c_void_p])
 
-_lib.register("dn_adam_pack", [_lib.c_void_p] * 4 + [_lib.c_long, _lib.c_float, _lib.c_double,
-                               _lib.c_double, _lib.c_float, _lib.c_float, _lib.c_float,
-                               _lib.c_void_p, _lib.c_int, _lib.c_int, _lib.c_void_p, _lib.c_int,
-                               _lib.c_int, _lib.c_int, _lib.c_int, _lib.c_void_p, _lib.c_int,
-                               _lib.c_long, _lib.c_void_p, _lib.c_void_p, _lib.c_long,
-                               _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
-                               _lib.c_void_p, _lib.c_int, _lib.c_void_p, _lib.c_void_p,
-                               _lib.c_void_p, _lib.c_void_p, _lib.c_void_p, _lib.c_void_p,
-                               _lib.c_void_p])
+# (block, update, zero_grad, segs, cnt, I, Hd, HD, feed, xb, yd, sd, gofs, record, srcs, stream)
+_lib.register("dn_adam_pack", [_P, _I, _I, _P, _I, _I, _I, _I] + _FEED + [_P, _P, _P, _I, _P, _P, _P])
 _lib.register("dn_swap_f32", [_lib.c_void_p, _lib.c_void_p, _lib.c_long, _lib.c_void_p])
 _lib.register("dn_step_record", [_lib.c_void_p, _lib.c_int, _lib.c_void_p])
 
 
-def ctypes_addr(obj) -> int:
-    import ctypes
-    return ctypes.addressof(obj)
+ctypes_addr = ctypes.addressof
+
+
+# host mirrors of the optim.hip structs, each checked against the library where it is filled
+class _AdamArgs(ctypes.Structure):
+    _fields_ = ([(k, _P) for k in ("p", "g", "m", "v", "ema")] + [("n", _L)]
+                + [(k, _F) for k in ("lr", "b1", "b2", "eps", "wd", "grad_scale", "bc1",
+                                     "inv_sqrt_bc2")]
+                + [("b1d", _D), ("b2d", _D), ("tdev", _P), ("tofs", _I), ("pad", _I)]
+                + [(k, _P) for k in ("cursor", "cs", "ls", "es")])
+
+
+class _Seg(ctypes.Structure):  # PackSeg
+    _fields_ = [("off", _L), ("n", _I), ("kind", _I), ("d", _I), ("dst", _P), ("dst2", _P)]
+
+
+class _Src(ctypes.Structure):  # SlabSrc
+    _fields_ = [("slab", _P), ("elems", _L), ("M", _I), ("N", _I), ("splits", _I), ("mode", _I),
+                ("alpha", _F), ("beta", _F)]
+
+
+class _Rec(ctypes.Structure):  # StepRecord
+    _fields_ = [("out", _P), ("ld", _L), ("col", _I), ("B", _I), ("loss", _P), ("rs", _P),
+                ("rl", _P), ("n", _L), ("cursor", _P), ("pred", _P)]
 
 
 ALIGN = 4  # elements (16 bytes)
@@ -263,14 +272,8 @@ class FusedAdam:
         self._clip: Optional[torch.Tensor] = None
         self._max_grad_norm = c if c > 0 else None
         if c > 0:
-            dev = flat.data.device
-            if dev.type == "cuda":
-                L = _lib.lib()
-                L.dn_clip_state_size.restype = _lib.c_long
-                if (int(L.dn_clip_parts()) != CLIP_PARTS
-                        or int(L.dn_clip_state_size()) != (CLIP_PARTS + 2) * 8):
-                    raise RuntimeError("clip state layout mismatch with the kernel library")
-            self._clip = torch.zeros(CLIP_PARTS + 2, dtype=torch.float64, device=dev)
+            self._clip = self._state_block(CLIP_PARTS + 2, "dn_clip_state_size", torch.float64,
+                                           "clip state", dn_clip_parts=CLIP_PARTS)
             self._clip_f = self._clip[CLIP_PARTS:].view(torch.float32)
             self._clip_i = self._clip[CLIP_PARTS:].view(torch.int32)
             self._clip_f[0] = c
@@ -286,13 +289,7 @@ class FusedAdam:
         self.plateau_wait = 0  # validations without improvement (plateau_step)
         if lr_schedule is not None:
             self._sched = LrSchedule.of(lr_schedule).check(self._lr)
-            dev = flat.data.device
-            if dev.type == "cuda":
-                L = _lib.lib()
-                L.dn_lr_state_size.restype = _lib.c_long
-                if int(L.dn_lr_state_size()) != LR_WORDS * 4:
-                    raise RuntimeError("lr state layout mismatch with the kernel library")
-            self._lrs = torch.zeros(LR_WORDS, dtype=torch.int32, device=dev)
+            self._lrs = self._state_block(LR_WORDS, "dn_lr_state_size", torch.int32, "lr state")
             self._lrs_f = self._lrs.view(torch.float32)
             self._write_lr_state()
         if ema_decay is None:
@@ -305,16 +302,20 @@ class FusedAdam:
         self._ema_warmup = bool(ema_warmup)
         self._swapped = False  # flat.data holds the average, ema the raw parameters
         if d > 0:
-            dev = flat.data.device
-            if dev.type == "cuda":
-                L = _lib.lib()
-                L.dn_ema_state_size.restype = _lib.c_long
-                if int(L.dn_ema_state_size()) != EMA_WORDS * 4:
-                    raise RuntimeError("ema state layout mismatch with the kernel library")
+            self._emas = self._state_block(EMA_WORDS, "dn_ema_state_size", torch.int32,
+                                           "ema state")
             self.ema = flat.data.detach().clone()
-            self._emas = torch.zeros(EMA_WORDS, dtype=torch.int32, device=dev)
             self._emas_f = self._emas.view(torch.float32)
             self._write_ema_state()
+
+    def _state_block(self, words: int, size_symbol: str, dtype, what: str,
+                     **counts) -> torch.Tensor:
+        """A zeroed device state block of ``words`` ``dtype`` words (optim.hip ClipState / LrState
+        / EmaState), its layout checked against the library (``_lib.checked_struct``)."""
+        block = torch.zeros(words, dtype=dtype, device=self.flat.data.device)
+        if block.is_cuda:
+            _lib.checked_struct(words * block.element_size(), size_symbol, what, **counts)
+        return block
 
     # weight average -----------------------------------------------------------------------------
     def _write_ema_state(self):
@@ -336,7 +337,6 @@ class FusedAdam:
     def ema_decay(self, value: Optional[float]):
         on = value is not None and _check_ema_decay(value) > 0
         if on != (self.ema is not None):
-            self._need_ema("ema_decay")
             raise ValueError("FusedAdam.ema_decay: the weight average is switched on or off when "
                              "the optimizer is built (it changes what is launched)")
         if not on:
@@ -525,7 +525,7 @@ class FusedAdam:
                              "optimizer is built (it changes what is launched)")
         if not on:
             return
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        if _capturing():
             # the write would become a graph node that resets the threshold at every replay
             raise RuntimeError("FusedAdam.max_grad_norm set inside a HIP graph capture")
         self._max_grad_norm = float(value)
@@ -552,6 +552,19 @@ class FusedAdam:
     def zero_grad(self, set_to_none: bool = False):
         self.flat.zero_grad()
 
+    def _adam_args(self, grad_scale: float, clip: Optional[int], tofs: int,
+                   bc=None) -> _AdamArgs:
+        """The launch's argument block (optim.hip AdamArgs).  ``clip``: what :meth:`_sqnorm`
+        returned.  The update number is ``tofs`` past the device counter -- or, with ``bc`` (the
+        host's ``(bc1, 1 / sqrt(bc2))``), ``tofs`` itself."""
+        f, (b1, b2) = self.flat, self.betas
+        tdev, bc = (None, bc) if bc else (self._tdev.data_ptr(), (1.0, 1.0))
+        return _lib.checked_struct(_AdamArgs, "dn_adam_args_size", "adam argument block")(
+            f.data.data_ptr(), f.grad.data_ptr(), self.exp_avg.data_ptr(),
+            self.exp_avg_sq.data_ptr(), _lib.ptr(self.ema), f.data.numel(), self.lr, b1, b2,
+            self.eps, self.weight_decay, grad_scale, *bc, b1, b2, tdev, tofs, 0,
+            _lib.ptr(self.cursor), clip, _lib.ptr(self._lrs), _lib.ptr(self._emas))
+
     def step(self, grad_scale: float = 1.0):
         self._refuse_swapped()
         self.step_count += 1
@@ -560,12 +573,11 @@ class FusedAdam:
         bc2 = 1 - b2 ** self.step_count
         d = self.flat.data
         if d.is_cuda:
-            clip = self._sqnorm()
-            _lib.call("dn_adam", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
-                      self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
-                      self.weight_decay, bc1, 1.0 / math.sqrt(bc2), grad_scale,
-                      _lib.ptr(self.cursor), clip, self.step_count, _lib.ptr(self._lrs),
-                      _lib.ptr(self.ema), _lib.ptr(self._emas), _lib.stream())
+            # (the number only matters to the schedule and the average)
+            tofs = self.step_count if (self._lrs is not None or self._emas is not None) else 1
+            args = self._adam_args(grad_scale, self._sqnorm(), tofs,
+                                   bc=(bc1, 1.0 / math.sqrt(bc2)))
+            _lib.call("dn_adam", ctypes_addr(args), 0, _lib.stream())
             return
         lr = self.lr_at(self.step_count)
         if self._lrs is not None:  # (recorded for a skipped update too: it consumed its number)
@@ -591,7 +603,7 @@ class FusedAdam:
     # HIP-graph form --------------------------------------------------------------------------
     def sync_device_step(self):
         """Copy the host step count to the device counter :meth:`step_graphable` reads."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        if _capturing():
             # inside a capture the fill (and a first allocation) would become graph nodes that
             # reset the counter at every replay
             raise RuntimeError("FusedAdam.sync_device_step inside a HIP graph capture")
@@ -607,16 +619,10 @@ class FusedAdam:
         prologue launch before each replay), so the update is ONE graph node, not Adam + a
         one-thread bump kernel."""
         self._refuse_swapped()
-        d = self.flat.data
         if self._tdev is None:
             self.sync_device_step()
-        b1, b2 = self.betas
-        clip = self._sqnorm()
-        _lib.call("dn_adam_dev", d.data_ptr(), self.flat.grad.data_ptr(), self.exp_avg.data_ptr(),
-                  self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1, b2, self.eps,
-                  self.weight_decay, grad_scale, self._tdev.data_ptr(), int(prebumped),
-                  _lib.ptr(self.cursor), clip, _lib.ptr(self._lrs), _lib.ptr(self.ema),
-                  _lib.ptr(self._emas), _lib.stream())
+        args = self._adam_args(grad_scale, self._sqnorm(), 0 if prebumped else 1)
+        _lib.call("dn_adam", ctypes_addr(args), int(not prebumped), _lib.stream())
 
     # Adam that also emits the next step's operands (optim.hip adam_pack_kernel) ------------------
     def attach_pack(self, pack, src=None, xb: Optional[torch.Tensor] = None,
@@ -626,16 +632,8 @@ class FusedAdam:
         gather the next batch of ``src`` (``DeviceSource``) into ``xb`` / ``yd`` there too.
         ``sd`` (int64 [B + 1]): the next batch's dataset rows go there as well; ``copy_x=False``
         then skips the batch copy (the GEMMs read the rows in place: ``ops.gemm.rows_from``)."""
-        import ctypes
         rows = pack.rows(self.flat)
-
-        class _Seg(ctypes.Structure):
-            _fields_ = [("off", ctypes.c_long), ("n", ctypes.c_int), ("kind", ctypes.c_int),
-                        ("d", ctypes.c_int), ("dst", ctypes.c_void_p), ("dst2", ctypes.c_void_p)]
-        L = _lib.lib()
-        L.dn_pack_seg_size.restype = ctypes.c_long
-        if ctypes.sizeof(_Seg) != L.dn_pack_seg_size():
-            raise RuntimeError("pack segment layout mismatch with the kernel library")
+        _lib.checked_struct(_Seg, "dn_pack_seg_size", "pack segment")
         tab = (_Seg * max(1, len(rows)))()
         for i, (off, n, kind, d, dst, dst2) in enumerate(rows):
             tab[i] = _Seg(off, n, kind, d, dst, dst2 or None)
@@ -680,16 +678,7 @@ class FusedAdam:
 
     def _slab_table(self, cnt: int):
         """The ``optim.hip SlabSrc`` rows by segment for the accepted sources."""
-        import ctypes
-
-        class _Src(ctypes.Structure):
-            _fields_ = [("slab", ctypes.c_void_p), ("elems", ctypes.c_long), ("M", ctypes.c_int),
-                        ("N", ctypes.c_int), ("splits", ctypes.c_int), ("mode", ctypes.c_int),
-                        ("alpha", ctypes.c_float), ("beta", ctypes.c_float)]
-        L = _lib.lib()
-        L.dn_slab_src_size.restype = ctypes.c_long
-        if ctypes.sizeof(_Src) != L.dn_slab_src_size():
-            raise RuntimeError("slab source layout mismatch with the kernel library")
+        _lib.checked_struct(_Src, "dn_slab_src_size", "slab source")
         tab = (_Src * max(1, cnt))()
         for i, s in self._slab_srcs.items():
             tab[i] = _Src(s.slab, s.slab_elems, s.M, s.N, s.splits, s.mode, s.alpha, s.beta)
@@ -705,14 +694,11 @@ class FusedAdam:
         the recorder's rings at the cursor (one more workgroup of the same launch)."""
         self._refuse_swapped()
         pack, tab, cnt, src, xb, yd, sd, copy_x = self._pack
-        d = self.flat.data
         if self._tdev is None:
             self.sync_device_step()
-        b1, b2 = self.betas
         if src is not None:
-            gx = [src.X.data_ptr(), src._mode(xb), src.row,
-                  src.Y.data_ptr(), _lib.ptr(src.order), src.nb, src.cursor.data_ptr(), src.B,
-                  xb.data_ptr() if copy_x else None, yd.data_ptr(), _lib.ptr(sd)]
+            gx = src.feed_args(xb) + [xb.data_ptr() if copy_x else None, yd.data_ptr(),
+                                      _lib.ptr(sd)]
         else:
             gx = [None, 0, 0, None, None, 1, None, 0, None, None, None]
         clip = self._sqnorm() if update else None
@@ -723,13 +709,11 @@ class FusedAdam:
                                    "that cannot sum them (no update, or a clipped one)")
             srcs = self._slab_table(cnt)
         try:
-            _lib.call("dn_adam_pack", d.data_ptr(), self.flat.grad.data_ptr(),
-                      self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), d.numel(), self.lr, b1,
-                      b2, self.eps, self.weight_decay, grad_scale, self._tdev.data_ptr(),
-                      int(update), 1, ctypes_addr(tab), cnt, pack.I, pack.Hd, pack.HD, *gx,
-                      int(gofs), ctypes_addr(record) if (record is not None and update) else None,
-                      clip, _lib.ptr(self._lrs), ctypes_addr(srcs) if srcs is not None else None,
-                      _lib.ptr(self.ema), _lib.ptr(self._emas), _lib.stream())
+            args = self._adam_args(grad_scale, clip, 0)
+            _lib.call("dn_adam_pack", ctypes_addr(args), int(update), 1, ctypes_addr(tab), cnt,
+                      pack.I, pack.Hd, pack.HD, *gx, int(gofs),
+                      ctypes_addr(record) if (record is not None and update) else None,
+                      ctypes_addr(srcs) if srcs is not None else None, _lib.stream())
         finally:
             self.drop_slabs()  # (the launch is in the stream: the slabs may be reused after it)
 
@@ -894,13 +878,16 @@ class DeviceSource:
             return 1
         return 2 if xb.dtype == torch.float32 else 0
 
+    def feed_args(self, xb: torch.Tensor) -> list:
+        """The arguments ``X ... B`` every gathering launcher starts its device-feed tail with
+        (``prologue.h prologue_gather``)."""
+        return [self.X.data_ptr(), self._mode(xb), self.row, self.Y.data_ptr(),
+                _lib.ptr(self.order), self.nb, self.cursor.data_ptr(), self.B]
+
     def gather(self, xb: torch.Tensor, yd: torch.Tensor, grad: torch.Tensor,
                bump: Optional[torch.Tensor] = None):
         """The standalone device-fed prologue launch (``dn_step_gather``)."""
-        _lib.call("dn_step_gather", self.X.data_ptr(), self._mode(xb),
-                  self.row, self.Y.data_ptr(), _lib.ptr(self.order), self.nb,
-                  self.cursor.data_ptr(), self.B, xb.data_ptr(), yd.data_ptr(), grad.data_ptr(),
-                  grad.numel(), _lib.ptr(bump), _lib.stream())
+        _lib.call("dn_step_gather", *self.prologue_args(xb, yd, grad, bump), _lib.stream())
 
     def labels_of(self, steps: int) -> torch.Tensor:
         """Labels of batches ``0 .. steps-1`` of the current order, flattened (what a
@@ -911,32 +898,8 @@ class DeviceSource:
 
     def prologue_args(self, xb, yd, grad, bump=None):
         """Argument tail of ``dn_lstm_pack_gather`` (the prologue riding in the weight pack)."""
-        return [self.X.data_ptr(), self._mode(xb), self.row,
-                self.Y.data_ptr(), _lib.ptr(self.order), self.nb, self.cursor.data_ptr(),
-                self.B, xb.data_ptr(), yd.data_ptr(), grad.data_ptr(), grad.numel(),
-                _lib.ptr(bump)]
-
-
-_STEP_RECORD = None
-
-
-def _step_record_type():
-    """The ctypes layout of ``optim.hip StepRecord``, checked against the library once."""
-    global _STEP_RECORD
-    if _STEP_RECORD is None:
-        import ctypes
-
-        class _Rec(ctypes.Structure):
-            _fields_ = [("out", ctypes.c_void_p), ("ld", ctypes.c_long), ("col", ctypes.c_int),
-                        ("B", ctypes.c_int), ("loss", ctypes.c_void_p), ("rs", ctypes.c_void_p),
-                        ("rl", ctypes.c_void_p), ("n", ctypes.c_long), ("cursor", ctypes.c_void_p),
-                        ("pred", ctypes.c_void_p)]
-        L = _lib.lib()
-        L.dn_step_record_size.restype = ctypes.c_long
-        if ctypes.sizeof(_Rec) != L.dn_step_record_size():
-            raise RuntimeError("step record layout mismatch with the kernel library")
-        _STEP_RECORD = _Rec
-    return _STEP_RECORD
+        return self.feed_args(xb) + [xb.data_ptr(), yd.data_ptr(), grad.data_ptr(), grad.numel(),
+                                     _lib.ptr(bump)]
 
 
 class StepRecorder:
@@ -973,9 +936,9 @@ class StepRecorder:
         if (out.dim() != 2 or out.shape[0] != self.B or out.dtype != torch.float32
                 or not out.is_contiguous() or loss.dtype != torch.float32 or loss.numel() != 1):
             raise ValueError("StepRecorder: out must be contiguous fp32 [B, C], loss fp32 scalar")
-        rec = _step_record_type()(out.data_ptr(), out.shape[1], self.col, self.B, loss.data_ptr(),
-                                  self.scores.data_ptr(), self.losses.data_ptr(), self.n,
-                                  self.cursor.data_ptr(), pp)
+        rec = _lib.checked_struct(_Rec, "dn_step_record_size", "step record")(
+            out.data_ptr(), out.shape[1], self.col, self.B, loss.data_ptr(),
+            self.scores.data_ptr(), self.losses.data_ptr(), self.n, self.cursor.data_ptr(), pp)
         if len(self._cache) > 64:
             self._cache.clear()
         self._cache[key] = rec

@@ -96,7 +96,6 @@ class LowRankTable:
     def __init__(self, layers, device):
         import ctypes
         L = _lib.lib()
-        L.dn_lr_layer_size.restype = ctypes.c_long
         maxr, plds, qlds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         L.dn_lr_limits(ctypes.byref(maxr), ctypes.byref(plds), ctypes.byref(qlds))
 
@@ -104,8 +103,7 @@ class LowRankTable:
             _fields_ = [(k, ctypes.c_void_p) for k in ("G", "err", "P", "Psend", "Qsend", "norms",
                                                      "active", "iters")] + \
                        [(k, ctypes.c_int) for k in ("out", "in_", "r", "b1", "n1", "b3", "n3")]
-        if ctypes.sizeof(LrLayer) != L.dn_lr_layer_size():
-            raise RuntimeError("low-rank table layout mismatch with the kernel library")
+        _lib.checked_struct(LrLayer, "dn_lr_layer_size", "low-rank table")
         n = len(layers)
         if n > 256:
             raise ValueError("at most 256 low-rank layers per table")
@@ -222,10 +220,7 @@ class PiReconTable:
             _fields_ = [("G", ctypes.c_void_p), ("P", ctypes.c_void_p), ("Q", ctypes.c_void_p),
                         ("out", ctypes.c_int), ("inn", ctypes.c_int), ("r", ctypes.c_int),
                         ("start", ctypes.c_long)]
-        L = _lib.lib()
-        L.dn_pi_recon_size.restype = ctypes.c_long
-        if ctypes.sizeof(PiRecon) != L.dn_pi_recon_size():
-            raise RuntimeError("reconstruction table layout mismatch with the kernel library")
+        _lib.checked_struct(PiRecon, "dn_pi_recon_size", "reconstruction table")
         self.n = len(records)
         rec = (PiRecon * max(self.n, 1))()
         start = 0

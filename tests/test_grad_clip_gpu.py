@@ -110,11 +110,11 @@ def _ica(seed=0, hidden=128):
     return m
 
 
-def _packed_opt(clip, seed=0):
+def _packed_opt(clip, seed=0, ema=None):
     from dinunet_implementations_amd.ops import FlatParams, FusedAdam
     m = _ica(seed)
     flat = FlatParams(m.parameters())
-    opt = FusedAdam(flat, lr=1e-3, weight_decay=1e-4, max_grad_norm=clip)
+    opt = FusedAdam(flat, lr=1e-3, weight_decay=1e-4, max_grad_norm=clip, ema_decay=ema)
     pp = m.persistent_pack(flat.data.device)
     opt.attach_pack(pp)
     return m, flat, opt, pp
@@ -368,3 +368,51 @@ def test_threshold_setter_refuses_a_capture(monkeypatch):
         opt.max_grad_norm = 2.0
     monkeypatch.undo()
     assert opt.max_grad_norm == 1.0 and float(opt._clip_f[0]) == 1.0
+
+
+# ---- the launchers' argument block ---------------------------------------------------------------
+def test_argument_block_layout_and_refusals():
+    """The host mirror of optim.hip AdamArgs has the library's size, and every refusal Python can
+    reach is a DN_BAD_SHAPE status before any launch (the buffers stay as they were)."""
+    import ctypes
+    from dinunet_implementations_amd.ops import _lib
+    from dinunet_implementations_amd.ops.optim import _AdamArgs, _Src
+    L = _lib.lib()
+    L.dn_adam_args_size.restype = ctypes.c_long
+    assert int(L.dn_adam_args_size()) == ctypes.sizeof(_AdamArgs)
+    m, flat, opt, pp = _packed_opt(0.5, ema=0.9)
+    opt.sync_device_step()
+    opt.device_step().add_(1)
+    flat.grad.copy_(_grad(flat.grad.numel(), 0))
+    before = _state(flat, opt) + [opt.ema.clone(), flat.grad.clone(), pp.wih_p.clone()]
+    pack, tab, cnt = opt._pack[:3]
+    BAD, st = 1, _lib.stream()
+
+    def block(**fields):
+        a = opt._adam_args(1.0, opt._clip.data_ptr(), 0)
+        for k, v in fields.items():
+            setattr(a, k, v)
+        return a
+
+    def adam(a, bump=0):
+        return L.dn_adam(ctypes.addressof(a), bump, st)
+
+    def adam_pack(a, update, srcs=None):
+        return L.dn_adam_pack(ctypes.addressof(a), update, 1, ctypes.addressof(tab), cnt, pack.I,
+                              pack.Hd, pack.HD, None, 0, 0, None, None, 1, None, 0, None, None,
+                              None, 1, None, ctypes.addressof(srcs) if srcs else None, st)
+
+    n = flat.data.numel()
+    off = dict(p=flat.data.data_ptr() + 4, n=n - 4)  # (misaligned, and still inside the buffer)
+    assert adam(block(**off)) == BAD and adam_pack(block(**off), 1) == BAD
+    assert adam(block(es=None)) == BAD and adam_pack(block(es=None), 1) == BAD  # ema without state
+    assert adam(block(ema=None)) == BAD  # and the state without the average
+    assert adam(block(tdev=None), bump=1) == BAD  # nothing to advance
+    assert adam_pack(block(), 0) == BAD  # clip with update = 0
+    assert adam_pack(block(), 1, srcs=(_Src * cnt)()) == BAD  # slab sources with clip
+    assert adam_pack(block(cs=None), 0, srcs=(_Src * cnt)()) == BAD  # ... or without an update
+    torch.cuda.synchronize()
+    after = _state(flat, opt) + [opt.ema, flat.grad, pp.wih_p]
+    for a, b in zip(after, before):
+        assert torch.equal(a, b)
+    assert int(opt.skipped_steps) == 0

@@ -73,7 +73,13 @@ class LocalNode:
         for c in (self.cfg, {**self.cfg, **(self.cfg.get("pretrain_args") or {})}):
             # the file transport ships engine.payload(), which the private release (issued by
             # DSGDEngine.reduce on the collective path) never sees
-            from ..parallel.engines import dp_options
+            from ..parallel.engines import dp_options, secure_agg_option
+            if secure_agg_option(c):
+                # the pair keys would have to be agreed through the remote aggregator, which
+                # relays every file: out of scope
+                raise ValueError("secure_agg (the masked gradient sum) is implemented by the "
+                                 "in-process runtime (runtime.site); the COINSTAC phase machines "
+                                 "would ship the gradient in the clear")
             if dp_options(c)[0] > 0:
                 raise ValueError("dp_clip_norm (the private gradient release) is implemented by "
                                  "the in-process runtime (runtime.site); the COINSTAC phase "

@@ -112,6 +112,11 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     "dp_noise_multiplier": 0,
     "dp_delta": 1e-5,
     "dp_seed": None,
+    # secure aggregation (ops.secagg, dSGD only): every party sends a pairwise-masked uint64
+    # fixed-point image of its gradient; the masks cancel in the sum, so no party sees another's
+    # gradient and every party opens the same exact mean.  Where it is unset,
+    # DINUNET_SECURE_AGG=1 applies
+    "secure_agg": False,
     "rccl_algo": None,
     "rccl_proto": None,
     "collective_timeout_s": 1800,
@@ -415,6 +420,11 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     check_dp(cfg)
     if isinstance(cfg.get("pretrain_args"), dict):
         check_dp({**cfg, **cfg["pretrain_args"]})
+    sa = cfg.get("secure_agg")
+    sa = False if sa is None else sa
+    if not isinstance(sa, bool):
+        raise ValueError(f"secure_agg must be true or false, got {sa!r}")
+    cfg["secure_agg"] = sa
     ls = cfg.get("label_smoothing", 0)
     ls = 0 if ls is None else ls
     if isinstance(ls, bool) or not isinstance(ls, (int, float)) or not (0 <= ls < 1):

@@ -53,7 +53,7 @@ namespace {
 
 constexpr int PX_MAXW = 16;
 constexpr int HDR = 8, SB = 2048, SBS = HDR + SB;  // as payload.hip
-constexpr int PT_BF16 = 0, PT_F16 = 1, PT_F32 = 2;
+constexpr int PT_BF16 = 0, PT_F16 = 1, PT_F32 = 2, PT_U64 = 3;
 
 template <int T> struct Wire;
 template <> struct Wire<PT_BF16> { typedef bf16x8 v8; typedef bf16 s; };
@@ -345,6 +345,113 @@ __global__ void __launch_bounds__(256) px_unpack_kernel(PxArgs a) {
   px_unpack_task<T>(a, blockIdx.y, blockIdx.x);
 }
 
+// ---- uint64 wire (the secure aggregation's masked residues, ops/secagg.py) -----------------------
+// The same three phases, flags, waits and slot layout ([8-word header | 2,048 words], the header
+// unused) with 8-byte words: push copies my words into the owner's inbox, reduce is the
+// wrap-around (mod 2^64) sum of the W inbox slots, unscaled, into every site's gather slot, unpack
+// is a copy.  src / dst of PxArgs point at uint64 words; n counts them (a multiple of 4).
+
+typedef unsigned long long px_u64;
+typedef px_u64 px_u64x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ char* px_u64_at(void* base, long words) {
+  return reinterpret_cast<char*>(base) + words * 8;
+}
+
+// 8 words at word offset `at` + 8 * i8 of a peer-written region (as px_ldw8)
+__device__ __forceinline__ void px_ldq8(const void* base, long at, long i8, int mode,
+                                        px_u64 (&o)[8]) {
+  const char* p = px_u64_at(const_cast<void*>(base), at);
+  if (!(mode & 2)) {
+    const px_u64x2* q = reinterpret_cast<const px_u64x2*>(p) + 4 * i8;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const px_u64x2 v = q[k];
+      o[2 * k] = v[0];
+      o[2 * k + 1] = v[1];
+    }
+    return;
+  }
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0,
+                                                                     0x7fffffff, 0x00020000);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const px_u64x2 v = __builtin_bit_cast(
+        px_u64x2, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(64 * i8 + 16 * k), 0, 17));
+    o[2 * k] = v[0];
+    o[2 * k + 1] = v[1];
+  }
+}
+
+__device__ __forceinline__ void px_stq8(void* base, long at, long i8, const px_u64 (&o)[8]) {
+  px_u64x2* q = reinterpret_cast<px_u64x2*>(px_u64_at(base, at)) + 4 * i8;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q[k] = px_u64x2{o[2 * k], o[2 * k + 1]};
+}
+
+__global__ void __launch_bounds__(256) px_push_u64_kernel(PxArgs a) {
+  const int s = blockIdx.x, d = blockIdx.y;
+  const long nsbc = a.chunk / SB;
+  const px_u64* x = reinterpret_cast<const px_u64*>(a.src);
+  const long e0 = d * a.chunk + (long)s * SB + 8 * threadIdx.x;
+  px_u64 o[8];
+  if (e0 + 8 <= a.n) {
+    const px_u64x2* q = reinterpret_cast<const px_u64x2*>(x + e0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const px_u64x2 v = q[k];
+      o[2 * k] = v[0];
+      o[2 * k + 1] = v[1];
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = e0 + k < a.n ? x[e0 + k] : 0ull;
+  }
+  px_stq8(a.inbox[d], ((long)a.me * nsbc + s) * SBS, 1 + threadIdx.x, o);
+  px_drain_release(a.mode);
+  if (threadIdx.x == 0) px_set(a.flags[d] + (long)s * a.W + a.me, 1u);
+}
+
+__global__ void __launch_bounds__(256) px_reduce_u64_kernel(PxArgs a) {
+  const int s = blockIdx.x, W = a.W;
+  const long nsbc = a.chunk / SB;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < W; ++w) px_take(a.flags[a.me] + (long)s * W + w, a, 0x100u | (unsigned)w);
+  px_acquire_join(a.mode);
+  const void* in = a.inbox[a.me];
+  px_u64 acc[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, v[8];
+  for (int w = 0; w < W; ++w) {
+    px_ldq8(in, ((long)w * nsbc + s) * SBS, 1 + threadIdx.x, a.mode, v);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] += v[k];
+  }
+  const long at = ((long)a.me * nsbc + s) * SBS;
+  for (int j = 0; j < W; ++j) px_stq8(a.gath[j], at, 1 + threadIdx.x, acc);
+  px_drain_release(a.mode);
+  if (threadIdx.x == 0)
+    for (int j = 0; j < W; ++j) px_set(a.flags[j] + nsbc * W + (long)a.me * nsbc + s, 1u);
+}
+
+__global__ void __launch_bounds__(256) px_unpack_u64_kernel(PxArgs a) {
+  const int s = blockIdx.x, d = blockIdx.y;
+  const long nsbc = a.chunk / SB;
+  if (threadIdx.x == 0)
+    px_take(a.flags[a.me] + nsbc * a.W + (long)d * nsbc + s, a, 0x200u | (unsigned)d);
+  px_acquire_join(a.mode);
+  const long e0 = d * a.chunk + (long)s * SB + 8 * threadIdx.x;
+  if (e0 >= a.n) return;
+  px_u64 o[8];
+  px_ldq8(a.gath[a.me], ((long)d * nsbc + s) * SBS, 1 + threadIdx.x, a.mode, o);
+  px_u64* dst = reinterpret_cast<px_u64*>(a.dst);
+  if (e0 + 8 <= a.n) {
+    px_stq8(dst, e0, 0, o);
+  } else {  // n is a multiple of 4: whole 16-byte pairs
+#pragma unroll
+    for (int k = 0; k < 8; k += 2)
+      if (e0 + k + 2 <= a.n) reinterpret_cast<px_u64x2*>(dst + e0)[k / 2] = px_u64x2{o[k], o[k + 1]};
+  }
+}
+
 // ---- separate waits -------------------------------------------------------------------------
 // When site processes SHARE a GPU (the one-GPU rehearsal), a launch whose every workgroup waits
 // holds a wave slot on many CUs while it waits -- and a peer's persistent LSTM workgroup, which
@@ -545,6 +652,16 @@ DN_API int dn_peer_launch(const PxArgs* args, int phase, int type, hipStream_t s
   if (phase >= 3 && a.chunk < a.n) return DN_BAD_SHAPE;
   if (phase == 4 && a.dstride < a.n) return DN_BAD_SHAPE;
   const dim3 gw((unsigned)nsb, (unsigned)a.W), g1((unsigned)nsb);
+  if (type == PT_U64) {  // the site-mean phases only; n counts 8-byte words in whole pairs
+    if (a.n % 2) return DN_BAD_SHAPE;
+    switch (phase) {
+      case 0: hipLaunchKernelGGL(px_push_u64_kernel, gw, dim3(256), 0, st, a); break;
+      case 1: hipLaunchKernelGGL(px_reduce_u64_kernel, g1, dim3(256), 0, st, a); break;
+      case 2: hipLaunchKernelGGL(px_unpack_u64_kernel, gw, dim3(256), 0, st, a); break;
+      default: return DN_BAD_SHAPE;
+    }
+    return dn_launch_status();
+  }
   switch (phase) {
     case 0: DN_PX_DISPATCH(type, px_push_kernel, gw, dim3(256), 0, st, a); break;
     case 1: DN_PX_DISPATCH(type, px_reduce_kernel, g1, dim3(256), 0, st, a); break;

@@ -8,6 +8,7 @@ from .lstm import bilstm as _bilstm_fused, lstm_supported, padded_hidden
 from .optim import (DeviceSource, FlatParams, FusedAdam, LrSchedule, StepRecorder,
                     cast_bf16_to_f32, cast_f32_to_bf16, step_prologue)
 from .dp import DPState
+from .secagg import SecAggState
 from .heads import softmax_ce, log_softmax_nll
 from .head import HeadSpec, check_loss_options, head_loss
 from .layernorm import LayerNorm, layer_norm
@@ -22,6 +23,6 @@ def bilstm(x, params, reduce: str = "none", modules=None, packed=None, xp=None,
 __all__ = [
     "LayerNorm", "layer_norm",
     "mm", "linear_bias_relu", "bilstm", "lstm_supported", "padded_hidden", "FlatParams",
-    "DeviceSource", "StepRecorder", "FusedAdam", "DPState", "LrSchedule", "cast_bf16_to_f32", "cast_f32_to_bf16", "step_prologue", "HeadSpec", "head_loss",
+    "DeviceSource", "StepRecorder", "FusedAdam", "DPState", "SecAggState", "LrSchedule", "cast_bf16_to_f32", "cast_f32_to_bf16", "step_prologue", "HeadSpec", "head_loss",
     "softmax_ce", "log_softmax_nll", "native_available", "capture", "reference",
 ]

@@ -241,3 +241,129 @@ def dp_privatize(grad: Tensor, clip_norm: float, noise_multiplier: float, seed: 
     if s != 0.0:
         out = out + (s * c) * dp_noise(flat.numel(), seed, stream, t)
     return out.view(grad.shape)
+
+
+# ---- secure aggregation: pairwise-masked integer sums (csrc/kernels/secagg.hip) -------------------
+SA_FRAC_BITS = 40        # q = int64(rint(g * 2^40))
+SA_CLAMP = 2.0 ** 18     # |g| is clamped to 2^18 (counted as saturated)
+SA_TAIL = 8              # the wire's extra block: [non-finite flag, saturated count, 0 x 6]
+SA_MAX_PARTIES = 16      # 16 * 2^58 < 2^63
+_CHACHA_CONST = (0x61707865, 0x3320646E, 0x79622D32, 0x6B206574)  # "expand 32-byte k"
+
+
+def chacha20_blocks(key, blocks, w13: int, w14: int, w15: int):
+    """The ChaCha20 block function (20 rounds, RFC 7539 state layout) for every block index of
+    ``blocks``: words 0-3 the constants, 4-11 the 256-bit ``key`` (32 bytes, or 8 uint32 words),
+    12 the block index, 13-15 as given.  Returns the output words as uint32 ``[len(blocks), 16]``
+    (their little-endian bytes are the key stream)."""
+    import numpy as np
+    if isinstance(key, (bytes, bytearray)):
+        if len(key) != 32:
+            raise ValueError("chacha20_blocks: a 32-byte key is required")
+        key = np.frombuffer(bytes(key), dtype="<u4")
+    key = np.asarray(key, dtype=np.uint32).reshape(8)
+    b = np.asarray(blocks, dtype=np.uint64).reshape(-1)
+    if b.size and int(b.max()) > 0xFFFFFFFF:
+        raise ValueError("chacha20_blocks: the block index is a 32-bit word")
+    nb = b.size
+    init = np.empty((16, nb), dtype=np.uint32)
+    for i, c in enumerate(_CHACHA_CONST):
+        init[i] = c
+    for i in range(8):
+        init[4 + i] = key[i]
+    init[12] = b.astype(np.uint32)
+    init[13], init[14], init[15] = (np.uint32(int(w) & 0xFFFFFFFF) for w in (w13, w14, w15))
+    x = [init[i].copy() for i in range(16)]
+
+    def rotl(v, r):
+        return (v << np.uint32(r)) | (v >> np.uint32(32 - r))
+
+    def qr(a, b_, c, d):
+        x[a] += x[b_]; x[d] = rotl(x[d] ^ x[a], 16)
+        x[c] += x[d]; x[b_] = rotl(x[b_] ^ x[c], 12)
+        x[a] += x[b_]; x[d] = rotl(x[d] ^ x[a], 8)
+        x[c] += x[d]; x[b_] = rotl(x[b_] ^ x[c], 7)
+
+    with np.errstate(over="ignore"):
+        for _ in range(10):
+            qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15)
+            qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14)
+        out = np.stack(x, axis=1)
+        out += init.T
+    return out
+
+
+def secagg_domain(fold: int, phase: int) -> int:
+    """The generator's domain word (state word 15) of a fold and phase (1: pretraining)."""
+    return (int(fold) * 4096 + int(bool(phase)) * 2048) & 0xFFFFFFFF
+
+
+def secagg_prg(key, n: int, t: int, domain: int):
+    """The pair mask of release ``t`` (1-based) for a wire of ``n`` data words plus the tail
+    block, as uint64 ``[n + 8]``: block ``b``'s 16 little-endian output words are the 8 masks of
+    elements ``8b .. 8b+7``; the tail block is ``b = ceil(n / 8)`` and sits at word ``n``."""
+    import numpy as np
+    n, t = int(n), int(t)
+    nb = -(-n // 8)
+    w = chacha20_blocks(key, np.arange(nb + 1, dtype=np.uint64), t & 0xFFFFFFFF,
+                        (t >> 32) & 0xFFFFFFFF, domain)
+    m = np.ascontiguousarray(w).astype("<u4").view("<u8").reshape(-1).astype(np.uint64)
+    return np.concatenate([m[:n], m[8 * nb:8 * nb + SA_TAIL]])
+
+
+def secagg_quantize(grad):
+    """``(wire, saturated, nonfinite)`` of one party's fp32 gradient before masking: uint64
+    ``[n + 8]`` residues of ``int64(rint(clamp(g, +-2^18) * 2^40))`` (a non-finite element: 0),
+    then the tail block ``[nonfinite 0/1, saturated count, 0 x 6]``."""
+    import numpy as np
+    g = np.ascontiguousarray(torch.as_tensor(grad).detach().cpu().reshape(-1).numpy(),
+                             dtype=np.float32)
+    fin = np.isfinite(g)
+    sat = fin & (np.abs(g) > np.float32(SA_CLAMP))
+    v = np.where(fin, np.clip(g, np.float32(-SA_CLAMP), np.float32(SA_CLAMP)), np.float32(0))
+    with np.errstate(all="ignore"):
+        q = np.rint(v.astype(np.float32) * np.float32(2.0 ** SA_FRAC_BITS)).astype(np.int64)
+    nonfinite, saturated = int(not fin.all()), int(sat.sum())
+    tail = np.zeros(SA_TAIL, dtype=np.int64)
+    tail[0], tail[1] = nonfinite, saturated
+    return np.concatenate([q, tail]).view(np.uint64), saturated, nonfinite
+
+
+def secagg_mask(grad, keys, rank: int, t: int, domain: int):
+    """Party ``rank``'s wire buffer of release ``t``: ``q + sum_{j > rank} PRG(k_j) - sum_{j <
+    rank} PRG(k_j)`` mod 2^64 with ``keys[j]`` the pair key shared with party ``j``
+    (``keys[rank]`` is not read).  uint64 ``[n + 8]``."""
+    import numpy as np
+    wire, _, _ = secagg_quantize(grad)
+    n = wire.size - SA_TAIL
+    with np.errstate(over="ignore"):
+        for j, k in enumerate(keys):
+            if j == rank:
+                continue
+            m = secagg_prg(k, n, t, domain)
+            wire = wire + m if j > rank else wire - m
+    return wire
+
+
+def secagg_open(total, world: int):
+    """``(mean fp32 [n], saturated, nonfinite)`` of the mod-2^64 sum ``total`` (uint64 ``[n +
+    8]``) of ``world`` parties' wire buffers: ``fp32(double(int64(sum)) * (2^-40 / world))``; all
+    NaN when the summed non-finite word is not 0."""
+    import numpy as np
+    total = np.asarray(total).view(np.uint64).reshape(-1)
+    n = total.size - SA_TAIL
+    c = 2.0 ** -SA_FRAC_BITS / int(world)
+    s = total.view(np.int64)
+    mean = (s[:n].astype(np.float64) * c).astype(np.float32)
+    nonfinite, saturated = int(s[n] != 0), int(s[n + 1])
+    if nonfinite:
+        mean = np.full(n, np.nan, dtype=np.float32)
+    return torch.from_numpy(mean), saturated, nonfinite
+
+
+def secagg_mean(grads):
+    """The opened mean of the parties' gradients (what every party holds after a release)."""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        total = sum(secagg_quantize(g)[0] for g in grads)
+    return secagg_open(total, len(grads))

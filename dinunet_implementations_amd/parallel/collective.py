@@ -186,6 +186,47 @@ class DirectMean:
         return self.n * self.send.element_size()  # this site's payload
 
 
+class DirectSum:
+    """The integer sibling of :class:`DirectMean` for the secure aggregation's wire: the
+    wrap-around (mod 2^64) sum over sites of ``n`` int64 words, left on every site.
+    ``all_to_all`` of int64 chunks, a local add (torch's int64 add wraps on CPU and GPU alike),
+    then ``all_gather`` -- issued from the host, through the process group, so the sum is formed
+    by this project's own arithmetic and not by a library's signed reduction."""
+
+    def __init__(self, group, n: int, device):
+        self.group = group
+        self.n = int(n)
+        W = group.world
+        self.chunk = -(-self.n // W)
+        self.send = torch.zeros(W * self.chunk, dtype=torch.int64, device=device)
+        self.recv = torch.zeros_like(self.send)
+        self.mine = torch.zeros(self.chunk, dtype=torch.int64, device=device)
+
+    def _a2a(self):
+        g = self.group
+        if g.backend == "gloo" and self.send.is_cuda:  # one-GPU multi-site rehearsal
+            r = torch.empty(self.recv.numel(), dtype=torch.int64)
+            dist.all_to_all_single(r, self.send.cpu(), group=g.pg)
+            self.recv.copy_(r)
+        else:
+            dist.all_to_all_single(self.recv, self.send, group=g.pg)
+
+    def run_(self, x: Tensor) -> int:
+        """``x`` (int64, ``n`` words, contiguous) <- the sum over sites mod 2^64."""
+        if x.dtype != torch.int64 or x.numel() != self.n or not x.is_contiguous():
+            raise ValueError(f"DirectSum.run_: {self.n} contiguous int64 words expected")
+        W, c = self.group.world, self.chunk
+        self.send[:self.n].copy_(x.reshape(-1))
+        self._a2a()
+        rows = self.recv.view(W, c)
+        self.mine.copy_(rows[0])
+        for w in range(1, W):
+            self.mine.add_(rows[w])
+        self.group.all_gather_into(self.send, self.mine)
+        x.reshape(-1).copy_(self.send[:self.n])
+        return self.n * 8  # this site's payload
+
+
 class _EventWork:
     """``Work``-like handle of an exchange running on a side stream."""
 

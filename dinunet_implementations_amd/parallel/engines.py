@@ -34,8 +34,9 @@ from ..ops import _lib
 from ..ops import capture as _cap
 from ..ops.dp import DPState
 from ..ops.optim import FlatParams
-from .collective import (PAYLOAD_TYPES, SB, DirectMean, from_payload, launch_on, payload_name,
-                         payload_numel, to_payload)
+from ..ops.secagg import SecAggState
+from .collective import (PAYLOAD_TYPES, SB, DirectMean, DirectSum, from_payload, launch_on,
+                         payload_name, payload_numel, to_payload)
 from .group import SiteGroup
 from .lowrank import EPS as EPS_MGS
 from .lowrank import LowRankTable, PiReconTable, _mgs_torch_, dad_factors, orthonormalize_
@@ -62,11 +63,25 @@ def dp_options(cfg: dict) -> Tuple[float, float]:
     return c, s
 
 
+def secure_agg_option(cfg: dict) -> bool:
+    """Is ``secure_agg`` on in ``cfg``?  Where the key is unset (None / false) the
+    ``DINUNET_SECURE_AGG=1`` switch applies."""
+    v = cfg.get("secure_agg")
+    if v is not None and not isinstance(v, bool):
+        raise ValueError(f"secure_agg must be true or false, got {v!r}")
+    return bool(v) or os.environ.get("DINUNET_SECURE_AGG", "") == "1"
+
+
+_WARNED_TWO_PARTIES = False
+
+
 class Engine:
     name = "base"
     # does the engine release a gradient (ops.dp can privatise it)?  The low-rank engines share
     # factors / activations instead
     supports_dp = False
+    # ... and can ops.secagg mask it?
+    supports_secure_agg = False
 
     def __init__(self, model: nn.Module, flat: FlatParams, group: SiteGroup, cfg: Optional[dict] = None):
         self.model = model
@@ -89,6 +104,24 @@ class Engine:
         if coll not in COLLECTIVES:
             raise ValueError(f"dsgd_collective {coll!r}: expected one of {', '.join(COLLECTIVES)}")
         self.collective = coll
+        # secure aggregation (ops.secagg, dSGD only): on / off is fixed here, the device block
+        # and the key agreement follow in DSGDEngine
+        self.sa: Optional[SecAggState] = None
+        self.secure_agg = secure_agg_option(self.cfg)
+        if self.secure_agg:
+            if not self.supports_secure_agg:
+                raise ValueError(f"secure_agg: the masked gradient sum is implemented for dSGD "
+                                 f"only ({self.name} shares factors, not a gradient)")
+            if self.half:
+                raise ValueError(f"secure_agg: the wire is the uint64 fixed-point image of the "
+                                 f"fp32 gradient; a {self.wire} payload (precision_bits=16 / "
+                                 f"payload_dtype) does not combine with it")
+            if coll == "allreduce":
+                raise ValueError("secure_agg: dsgd_collective='allreduce' would form the sum in "
+                                 "a library's signed arithmetic; use auto, peer or direct")
+            if group.world > SecAggState.MAX_PARTIES:
+                raise ValueError(f"secure_agg: at most {SecAggState.MAX_PARTIES} parties (sums of "
+                                 f"more do not fit int64), got {group.world}")
         self.peer = self._want_peer(coll)
         # differentially private release (ops.dp): on / off is fixed here.  The generator's
         # stream word fold * 4096 + phase * 2048 + global rank (phase 1: pretraining) keeps every
@@ -123,7 +156,8 @@ class Engine:
                 raise ValueError("dsgd_collective='peer' needs GPU sites and the kernel library "
                                  f"(at most 16 sites); device {self.flat.grad.device}")
             return True
-        return coll in ("auto", "calibrate") and self.half and self._peer_ok()
+        return (coll in ("auto", "calibrate")
+                and (self.half or (self.secure_agg and self.group.world > 1)) and self._peer_ok())
 
     # collective path -------------------------------------------------------------------------
     @property
@@ -224,6 +258,7 @@ class DSGDEngine(Engine):
     """
     name = "dSGD"
     supports_dp = True
+    supports_secure_agg = True
 
     def __init__(self, model, flat, group, cfg=None, bucket_mb: Optional[float] = None,
                  overlap: bool = True):
@@ -263,10 +298,16 @@ class DSGDEngine(Engine):
         # whichever captured form measures faster on this job's buckets and links
         coll = self.collective
         self.calibration: Optional[dict] = None
-        if coll == "calibrate":
+        sa_on = self.secure_agg and group.world > 1  # (one party: nothing leaves, no masks)
+        if coll == "calibrate" and sa_on:
+            coll = "peer" if self.peer else "direct"
+            self.calibration = {"choice": coll, "reason": "secure_agg: one captured form (the "
+                                "uint64 peer exchange), nothing to time"}
+        elif coll == "calibrate":
             coll = self._calibrate()
             self.peer = coll == "peer"
-        self.direct = (not self.peer) and (coll == "direct" or (coll == "auto" and self.half))
+        self.direct = (not self.peer) and (coll == "direct" or (coll == "auto" and self.half)
+                                           or sa_on)
         if self.half and not self.direct and not self.peer and self.wire == "fp16":
             # RCCL sums an all-reduce buffer in its own type: unscaled fp16 would flush
             # gradients below ~6e-8 and overflow past 65504 in the sum over sites, and a
@@ -288,15 +329,17 @@ class DSGDEngine(Engine):
         self.prefers_split = not self.peer
         if self.peer and len(self.buckets) > 1 and bool(self.cfg.get("peer_one_bucket", True)):
             self._set_buckets([(self.buckets[-1][0], self.buckets[0][1])])
+        if sa_on:
+            self._secagg_build()
         self._peer_build()
         self._hooks = []
         self._delivered = set()
         self.early_launches = 0  # buckets started before reduce() (observability)
         self._in_reduce = False
-        if self.dp is not None:
-            # nothing leaves the site before reduce() has privatised the gradient: no hook-issued
-            # launches, no split for the sake of an early bucket, and launch_bucket only records
-            # readiness (as the peer path already behaves)
+        if self.dp is not None or self.sa is not None:
+            # nothing leaves the site before reduce() has privatised / masked the gradient: no
+            # hook-issued launches, no split for the sake of an early bucket, and launch_bucket
+            # only records readiness (as the peer path already behaves)
             self.overlap = False
             self.prefers_split = False
         if self.peer:
@@ -325,6 +368,31 @@ class DSGDEngine(Engine):
         if not self.group.distributed or self.peer:
             return True
         return self.group.backend == "nccl" and not self.direct
+
+    def _secagg_build(self):
+        """The masked release of the whole gradient as ONE exchange: the key agreement (one
+        all-gather of public keys over the process group, ``parallel.secagg``), the device block
+        and the wire buffer.  Every rank is a party (a site's replicas count separately)."""
+        global _WARNED_TWO_PARTIES
+        from . import secagg as _keys
+        g, grad = self.group, self.flat.grad
+        if grad.numel() % 4:
+            raise ValueError("secure_agg: the flat gradient must hold a multiple of 4 elements")
+        if g.world == 2 and not _WARNED_TWO_PARTIES:
+            import warnings
+            _WARNED_TWO_PARTIES = True
+            warnings.warn("secure_agg with 2 parties: the sum reveals the peer's gradient to "
+                          "each of them (own + peer = sum)", RuntimeWarning, stacklevel=3)
+        fold, phase = int(self.cfg.get("dp_fold", 0)), int(bool(self.cfg.get("dp_phase", 0)))
+        keys = _keys.agree(g, fold, phase)
+        from ..ops import reference as _ref
+        self.sa = SecAggState(grad.device, g.world, g.rank, keys, _ref.secagg_domain(fold, phase))
+        del keys
+        self._sa_wire = self.sa.wire_like(grad)
+        self._sa_sum: Optional[DirectSum] = None
+        self.sa_transport = "peer" if self.peer else "direct"
+        self.sa_logged = 0  # saturated count already reported per epoch (runtime.site)
+        self._set_buckets([(0, self.flat.numel)])
 
     def _calibrate(self) -> str:
         """``dsgd_collective="calibrate"``: time the site-mean forms the step can run on THIS
@@ -530,16 +598,23 @@ class DSGDEngine(Engine):
     def _peer_build(self):
         """The peer exchange of every bucket, built now (arena regions and the IPC handle
         exchange are host work, never inside a capture; every site builds in the same order)."""
-        if self.peer:
+        if self.peer and self.sa is not None:
+            self._sa_peer()
+        elif self.peer:
             for s, e in self.buckets:
                 self._peer_mean(("bucket", s, e), e - s)
+
+    def _sa_peer(self):
+        from . import peer as _peer
+        return _peer.mean(self.group, self.flat.grad.device, self._sa_wire.numel(), _peer.U64,
+                          (self.name, "secagg"))
 
     def launch_bucket(self, b: int):
         """Mark bucket ``b`` ready and start every ready bucket up to it, in order (RCCL stream
         ordered after the current stream)."""
         if self.group.distributed:
             self._ready[b] = True
-            if self.dp is None:  # (private release: the buckets start in reduce())
+            if self.dp is None and self.sa is None:  # (else the exchange starts in reduce())
                 self._drain()
 
     def _launch(self, b: int):
@@ -592,6 +667,8 @@ class DSGDEngine(Engine):
         if not g.distributed:
             self._reset()
             return 1.0
+        if self.sa is not None:
+            return self._secagg_reduce()
         self._ready = [True] * len(self.buckets)
         self._in_reduce = True
         try:
@@ -613,6 +690,23 @@ class DSGDEngine(Engine):
         self.last_scale = 1.0 if (self.direct or self.peer) else 1.0 / g.world
         return self.last_scale
 
+    def _secagg_reduce(self) -> float:
+        """Mask (after the private release, if any), exchange the uint64 wire -- the peer
+        exchange's wrap-around sum, or the host-issued integer direct exchange -- and open: the
+        flat gradient then holds the mean, bit-identical on every party."""
+        grad, wire = self.flat.grad, self._sa_wire
+        self.sa.mask_(grad, wire)
+        if self.peer:
+            self.comm_bytes = self._sa_peer().run_(wire)
+        else:
+            if self._sa_sum is None:
+                self._sa_sum = DirectSum(self.group, wire.numel(), wire.device)
+            self.comm_bytes = self._sa_sum.run_(wire)
+        self.sa.open_(wire, grad)
+        self._reset()
+        self.last_scale = 1.0
+        return 1.0
+
     def close(self):
         for h in self._hooks:
             h.remove()
@@ -620,17 +714,26 @@ class DSGDEngine(Engine):
         _gradreg.unregister(self._on_grad)
 
     def state_dict(self):
-        return {} if self.dp is None else {"dp": self.dp.state_dict()}
+        sd = {} if self.dp is None else {"dp": self.dp.state_dict()}
+        if self.sa is not None:  # the release number and the counts; never a key
+            sd["secure_agg"] = self.sa.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
         if self.dp is not None and sd.get("dp"):
             self.dp.load_state_dict(sd["dp"])
+        if self.sa is not None and sd.get("secure_agg"):
+            self.sa.load_state_dict(sd["secure_agg"])
+            self.sa_logged = int(sd["secure_agg"].get("saturated", 0))
 
     # file transport
     def payload(self):
         if self.dp is not None:  # (compat/nodes.py refuses the option before it gets here)
             raise RuntimeError("dSGD payload(): the private gradient release runs in reduce(); "
                                "the file transport would ship the gradient as computed")
+        if self.secure_agg:  # (compat/nodes.py refuses the option before it gets here)
+            raise RuntimeError("dSGD payload(): secure_agg masks the gradient in reduce(); the "
+                               "file transport would ship it in the clear")
         g = self.flat.grad
         return {"grad": g.to(PAYLOAD_TYPES[self.wire][1]) if self.half else g.clone()}
 
@@ -1164,4 +1267,7 @@ def make_engine(name: str, model: nn.Module, flat: FlatParams, group: SiteGroup,
     if not cls.supports_dp and dp_options(dict(cfg or {}))[0] > 0:
         raise ValueError(f"dp_clip_norm: the private gradient release is implemented for dSGD "
                          f"only, not agg_engine {name!r} (it shares factors, not a gradient)")
+    if not cls.supports_secure_agg and secure_agg_option(dict(cfg or {})):
+        raise ValueError(f"secure_agg: the masked gradient sum is implemented for dSGD only, "
+                         f"not agg_engine {name!r} (it shares factors, not a gradient)")
     return cls(model, flat, group, cfg)

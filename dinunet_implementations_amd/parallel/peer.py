@@ -184,16 +184,24 @@ def arenas() -> List[PeerArena]:
     return list(_ARENAS)
 
 
+# the secure aggregation's wire (ops.secagg): uint64 residues, summed mod 2^64 and left unscaled
+# (peer.hip PT_U64); the exchanged tensor is int64, not fp32.  Not a ``payload_dtype``.
+U64 = "u64"
+_U64_CODE = 3
+
+
 def _elem(wire: str) -> int:
-    return 4 if wire == "fp32" else 2
+    return 8 if wire == U64 else (4 if wire == "fp32" else 2)
 
 
 class _Exchange:
     def __init__(self, ar: PeerArena, wire: str):
         self.ar = ar
         self.wire = wire
-        self.code, self.dtype = PAYLOAD_TYPES[wire]
+        self.code, self.dtype = (_U64_CODE, torch.int64) if wire == U64 else PAYLOAD_TYPES[wire]
         self.scaled = 1 if wire == "fp16" else 0
+        # what the caller hands in and gets back
+        self.xdtype = torch.int64 if wire == U64 else torch.float32
 
     def _args(self, inbox, gath, flags, src, dst, n, chunk, dstride=0, scale=1.0, a=None):
         a = _PxArgs() if a is None else a
@@ -215,12 +223,16 @@ class _Exchange:
 class PeerMean(_Exchange):
     """Mean over sites of an fp32 range of ``n`` elements, ``wire`` type on the links, fp32 sums.
     ``start`` (push) and ``finish`` (reduce + unpack) may be split around other work: the push
-    never waits, so the peers' data travel while this site computes."""
+    never waits, so the peers' data travel while this site computes.  With the ``u64`` wire the
+    range is ``n`` int64 words (a multiple of 4) and the result their wrap-around SUM over the
+    sites, unscaled (``scale`` is not read)."""
 
     def __init__(self, ar: PeerArena, n: int, wire: str):
         super().__init__(ar, wire)
         W = ar.W
         self.n = int(n)
+        if wire == U64 and self.n % 4:
+            raise ValueError("PeerMean: the u64 wire takes a multiple of 4 words")
         self.chunk = max(SB, -(-self.n // (SB * W)) * SB)
         self.nsbc = self.chunk // SB
         slot = payload_numel(self.chunk) * _elem(wire)
@@ -230,14 +242,14 @@ class PeerMean(_Exchange):
         self.bytes_sent = W * payload_numel(self.chunk) * _elem(wire)
 
     def start(self, x: torch.Tensor):
-        if x.numel() != self.n or x.dtype != torch.float32 or not x.is_contiguous():
-            raise ValueError(f"PeerMean.start: {self.n} contiguous fp32 elements expected")
+        if x.numel() != self.n or x.dtype != self.xdtype or not x.is_contiguous():
+            raise ValueError(f"PeerMean.start: {self.n} contiguous {self.xdtype} elements expected")
         self._launch(self._args(self.inbox, self.gath, self.flags, x.data_ptr(), 0, self.n,
                                 self.chunk), PUSH)
 
     def finish_args(self, x: torch.Tensor, scale: float = 1.0, into=None):
-        if x.numel() != self.n or x.dtype != torch.float32 or not x.is_contiguous():
-            raise ValueError(f"PeerMean.finish: {self.n} contiguous fp32 elements expected")
+        if x.numel() != self.n or x.dtype != self.xdtype or not x.is_contiguous():
+            raise ValueError(f"PeerMean.finish: {self.n} contiguous {self.xdtype} elements expected")
         return self._args(self.inbox, self.gath, self.flags, 0, x.data_ptr(), self.n, self.chunk,
                           scale=scale, a=into)
 

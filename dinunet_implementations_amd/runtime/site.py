@@ -432,6 +432,7 @@ class FederatedSite:
             if ema_on:  # the decay the epoch's last average used
                 logs.setdefault(f"{tag}ema_applied_decay", []).append(float(opt.applied_ema_decay))
             self._dp_log(engine, cfg, logs, tag)
+            self._sa_log(engine, logs, tag)
             tl.append([round(avg.average, 6)] + met.get((monitor if monitor != "loss" else "auc",)))
             logs.setdefault(f"{tag}samples_per_sec", []).append(nsamp / dt if dt > 0 else 0.0)
             stop = False
@@ -491,6 +492,7 @@ class FederatedSite:
         if step is not None and step.timers.summary():
             logs[f"{tag}phase_ms"] = step.timers.summary()  # DINUNET_PHASE_TIMERS=1
         self._dp_log(engine, cfg, logs, tag, final=True)
+        self._sa_log(engine, logs, tag, final=True)
         return best
 
     def _dp_engine_cfg(self, cfg: Dict[str, Any], fold: int, seed: int, phase: int) -> Dict[str, Any]:
@@ -532,6 +534,26 @@ class FederatedSite:
         for k in ("releases", "clipped", "nonfinite"):
             block[k] += int(prior.get(k, 0))
         logs["dp"] = block
+
+    @staticmethod
+    def _sa_log(engine, logs: Dict[str, Any], tag: str, final: bool = False):
+        """Secure aggregation on (``engine.sa``): per epoch ``secure_agg_saturated`` (elements
+        clamped to +-2^18 in the epoch's releases, summed over the parties -- the count every
+        party opens from the tail block); at the end of a phase the ``secure_agg`` block.  Absent
+        with the option off (and in a phase with one party, where nothing is masked)."""
+        sa = getattr(engine, "sa", None)
+        if sa is None:
+            return
+        if not final:
+            total = sa.saturated
+            logs.setdefault(f"{tag}secure_agg_saturated", []).append(total - engine.sa_logged)
+            engine.sa_logged = total
+            return
+        from ..ops import secagg as _sa
+        logs[f"{tag}secure_agg"] = {
+            "frac_bits": _sa.FRAC_BITS, "prg": "chacha20", "key_agreement": "x25519",
+            "parties": sa.world, "transport": engine.sa_transport, "releases": sa.releases,
+            "saturated": sa.saturated, "nonfinite": sa.nonfinite}
 
     def _device_feed(self, trainer: NNTrainer, step, engine, tr: DeviceLoader, bs: int, li: int,
                      steps: int, cfg: Dict[str, Any], fault_at) -> Optional[DeviceFeed]:

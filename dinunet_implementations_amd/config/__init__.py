@@ -71,6 +71,9 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     "dad_tol": 1e-3,
     "powersgd_rank": 4,
     "powersgd_warm_start": True,
+    # top-k sparsification (agg_engine "topK", ops.topk): the share of the gradient's elements a
+    # rank releases per step, in (0, 1]; k = min(n, max(1, ceil(topk_ratio * n)))
+    "topk_ratio": 0.01,
     # collective plan for the xGMI mesh (README "Collective plan"): dSGD bucket size, RCCL
     # algorithm / protocol (None = RCCL's own choice), per-collective timeout
     "dsgd_bucket_mb": 4.0,
@@ -394,10 +397,18 @@ def check_dp(cfg: Dict[str, Any]) -> None:
                          f"got {sd!r}")
 
 
+AGG_ENGINES = ("dSGD", "rankDAD", "powerSGD", "topK")
+
+
 def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     eng = cfg.get("agg_engine")
-    if eng not in ("dSGD", "rankDAD", "powerSGD"):
-        raise ValueError(f"unknown agg_engine {eng!r} (expected dSGD|rankDAD|powerSGD)")
+    if eng not in AGG_ENGINES:
+        raise ValueError(f"unknown agg_engine {eng!r} (expected {'|'.join(AGG_ENGINES)})")
+    tr = cfg.get("topk_ratio")
+    tr = 0.01 if tr is None else tr
+    if isinstance(tr, bool) or not isinstance(tr, (int, float)) or not (0 < tr <= 1):
+        raise ValueError(f"topk_ratio must be a number in (0, 1], got {tr!r}")
+    cfg["topk_ratio"] = tr
     if str(cfg.get("precision_bits")) not in ("16", "32"):
         raise ValueError("precision_bits must be '16' or '32'")
     cfg["precision_bits"] = str(cfg["precision_bits"])
@@ -486,7 +497,7 @@ def generate_compspec() -> Dict[str, Any]:
         "task_id": item("Task", "select", TASK_FS, values=[TASK_FS, TASK_ICA]),
         "mode": item("Mode", "select", "train", values=["train", "test"]),
         "agg_engine": item("Aggregation engine", "select", "dSGD", conditional=train,
-                           values=["dSGD", "rankDAD", "powerSGD"]),
+                           values=list(AGG_ENGINES)),
         "num_reducers": item("Reducer workers", "number", 2),
         "batch_size": item("Batch size", "number", 16),
         "local_iterations": item("Local iterations (grad accumulation)", "number", 1),
@@ -529,7 +540,8 @@ def generate_compspec() -> Dict[str, Any]:
             "id": "dinunet-mi355x",
             "version": "v0.1.0",
             "repository": "local",
-            "description": "FS-MLP / ICA-LSTM across sites with dSGD, rank-dAD or PowerSGD; "
+            "description": "FS-MLP / ICA-LSTM across sites with dSGD, rank-dAD, PowerSGD or "
+                           "top-k sparsification; "
                            "one MI355X per site, RCCL collectives over xGMI.",
         },
         "computation": {

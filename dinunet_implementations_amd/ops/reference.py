@@ -367,3 +367,49 @@ def secagg_mean(grads):
     with np.errstate(over="ignore"):
         total = sum(secagg_quantize(g)[0] for g in grads)
     return secagg_open(total, len(grads))
+
+
+# ---- top-k sparsified release with error feedback (csrc/kernels/topk.hip) --------------------------
+def _f32(a):
+    import numpy as np
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().reshape(-1).numpy()
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+
+
+def topk_k(n: int, ratio: float) -> int:
+    """``k = min(n, max(1, ceil(ratio * n)))``: the pairs a site releases per step."""
+    import math
+    return min(int(n), max(1, math.ceil(float(ratio) * int(n))))
+
+
+def topk_select(g, err, k: int):
+    """``(idx int32 [k], val fp32 [k], err_new fp32 [n])`` of one release: ``acc = g + err`` (one
+    fp32 add), ``key = bits(acc) & 0x7fffffff`` (NaN > inf > finite, +-0 tie); the ``k`` largest
+    keys are selected, the lower index winning among equal keys; the pairs come in ascending
+    index order; ``err_new`` is ``+0`` where selected and ``acc`` elsewhere."""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        acc = _f32(g) + _f32(err)
+    n, k = acc.size, int(k)
+    if not (1 <= k <= n):
+        raise ValueError(f"topk_select: k = {k} of n = {n}")
+    key = (acc.view(np.uint32) & np.uint32(0x7FFFFFFF)).astype(np.int64)
+    order = np.argsort(-key, kind="stable")  # (-key, i) ascending
+    idx = np.sort(order[:k]).astype(np.int32)
+    val = acc[idx].copy()
+    err_new = acc.copy()
+    err_new[idx] = np.float32(0.0)
+    return idx, val, err_new
+
+
+def topk_combine(pairs, n: int):
+    """The dense fp32 ``[n]`` sum of the ranks' ``(idx, val)`` pairs: ``out[i] = ((+0 + v_0) +
+    v_1) + ...`` over the ranks that selected ``i``, in rank order; ``+0`` elsewhere."""
+    import numpy as np
+    out = np.zeros(int(n), dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for idx, val in pairs:
+            idx = np.asarray(idx).astype(np.int64).reshape(-1)
+            out[idx] = out[idx] + _f32(val)  # (one rank's indices are distinct)
+    return out

@@ -1,4 +1,5 @@
-"""Gradient-aggregation engines: dSGD, rank-dAD, PowerSGD (reference ``comps/__init__.py:13-16``).
+"""Gradient-aggregation engines: dSGD, rank-dAD, PowerSGD (reference ``comps/__init__.py:13-16``)
+and top-k sparsification.
 
 Each engine turns every site's local gradient (living in the flat grad buffer of
 ``ops.FlatParams``) into the *global* update all sites apply with their own optimizer, so
@@ -11,6 +12,9 @@ replicas stay identical:
   Every other parameter (biases, BatchNorm) falls back to the dSGD mean.
 * ``powerSGD`` rank-r ``P = M Q`` / ``Q = M^T P`` with two all-reduces, warm-started ``Q`` and
   per-site error feedback (Vogels et al. 2019); vectors use the dSGD mean.
+* ``topK``     magnitude top-k sparsification with per-rank error feedback: every rank releases
+  the ``k = ceil(topk_ratio * n)`` largest entries of ``gradient + residual`` as (index, value)
+  pairs, one all-gather, and every rank sums the pairs in rank order (``ops.topk``).
 
 Every engine also exposes the three pieces the COINSTAC file transport needs
 (``payload`` on a site, ``aggregate`` on the remote, ``apply`` back on the site) with the same
@@ -35,6 +39,7 @@ from ..ops import capture as _cap
 from ..ops.dp import DPState
 from ..ops.optim import FlatParams
 from ..ops.secagg import SecAggState
+from ..ops.topk import FLOAT_INDEX_MAX, TopKState
 from .collective import (PAYLOAD_TYPES, SB, DirectMean, DirectSum, from_payload, launch_on,
                          payload_name, payload_numel, to_payload)
 from .group import SiteGroup
@@ -72,6 +77,16 @@ def secure_agg_option(cfg: dict) -> bool:
     return bool(v) or os.environ.get("DINUNET_SECURE_AGG", "") == "1"
 
 
+def topk_ratio_option(cfg: dict) -> float:
+    """``topk_ratio`` of ``cfg`` (default 0.01): the share of the gradient's elements a rank
+    releases per step, in (0, 1]."""
+    v = cfg.get("topk_ratio")
+    v = 0.01 if v is None else v
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0 < v <= 1):
+        raise ValueError(f"topk_ratio must be a number in (0, 1], got {v!r}")
+    return float(v)
+
+
 _WARNED_TWO_PARTIES = False
 
 
@@ -82,6 +97,8 @@ class Engine:
     supports_dp = False
     # ... and can ops.secagg mask it?
     supports_secure_agg = False
+    # what the engine puts on the wire instead (the refusals of the two options say it)
+    releases = "factors, not a gradient"
 
     def __init__(self, model: nn.Module, flat: FlatParams, group: SiteGroup, cfg: Optional[dict] = None):
         self.model = model
@@ -111,7 +128,7 @@ class Engine:
         if self.secure_agg:
             if not self.supports_secure_agg:
                 raise ValueError(f"secure_agg: the masked gradient sum is implemented for dSGD "
-                                 f"only ({self.name} shares factors, not a gradient)")
+                                 f"only ({self.name} shares {self.releases})")
             if self.half:
                 raise ValueError(f"secure_agg: the wire is the uint64 fixed-point image of the "
                                  f"fp32 gradient; a {self.wire} payload (precision_bits=16 / "
@@ -132,7 +149,7 @@ class Engine:
         if c > 0:
             if not self.supports_dp:
                 raise ValueError(f"dp_clip_norm: the private gradient release is implemented for "
-                                 f"dSGD only ({self.name} shares factors, not a gradient)")
+                                 f"dSGD only ({self.name} shares {self.releases})")
             # (``dp_rank``: the global rank of a site that trains alone in a group of its own)
             rank = int(self.cfg.get("dp_rank", group.rank))
             if not (0 <= rank < DP_STREAM_RANKS):
@@ -1256,7 +1273,129 @@ class PowerSGDEngine(Engine):
         return {k: sum(p[k].float() for p in payloads) / W for k in payloads[0]}
 
 
-ENGINES = {"dSGD": DSGDEngine, "rankDAD": RankDADEngine, "powerSGD": PowerSGDEngine}
+# =============================================================================================
+# top-k sparsification
+# =============================================================================================
+class TopKEngine(Engine):
+    """Magnitude top-k sparsification with error feedback (``ops.topk`` holds the contract).
+
+    Every rank is a contributor: replicas of a site each release the top-k of their own
+    gradient, and the divisor is the number of ranks.  One site still sparsifies and keeps the
+    residual, with no collective.  A non-finite element always wins the selection, leaves the
+    residual and reaches the update (``max_grad_norm`` then skips that step).
+
+    The exchange is one all-gather of ``2k`` 32-bit words per rank: inside the captured step
+    through the peer exchange (``dsgd_collective='peer'``, indices sent as fp32 values: exact up
+    to 2^24 elements), else host-issued through the process group after the replay."""
+    name = "topK"
+    releases = "top-k (index, value) pairs, not the dense gradient"
+
+    def __init__(self, model, flat, group, cfg=None):
+        super().__init__(model, flat, group, cfg)
+        if self.half:
+            raise ValueError(f"topK: the pairs travel as int32 indices and fp32 values; a "
+                             f"{self.wire} payload (precision_bits=16 / payload_dtype) is not "
+                             f"implemented")
+        self.ratio = topk_ratio_option(self.cfg)
+        grad = flat.grad
+        n = grad.numel()
+        if n >= 2 ** 31:
+            raise ValueError(f"topK: int32 indices address fewer than 2^31 elements, got {n}")
+        from ..ops import reference as _ref
+        self.k = _ref.topk_k(n, self.ratio)
+        # the selection runs on the device (csrc/kernels/topk.hip): the step may capture it
+        self.fast = bool(flat.data.is_cuda)
+        if self.peer and n > FLOAT_INDEX_MAX:
+            self.peer = False  # fp32 index words would not be exact
+        self.state = TopKState(grad.device, n, self.k, idx_float=self.peer)
+        g = group
+        if not g.distributed:
+            self.transport = "none (one site)"
+        elif self.peer:
+            self.transport = "peer gather (captured)"
+        else:
+            self.transport = "all-gather (host-issued)"
+        import logging
+        logging.getLogger(__name__).info("topK: k = %d of %d elements (ratio %g), exchange: %s",
+                                         self.k, n, self.ratio, self.transport)
+        if g.distributed:
+            self.state.gather_buffer(g.world)
+        if self.peer:  # the exchange region, built outside any capture (peer.PeerArena)
+            self._peer_gather()
+
+    def _peer_gather(self):
+        from . import peer as _peer
+        return _peer.gather(self.group, self.flat.grad.device, 2 * self.k, "fp32",
+                            (self.name, "pairs"))
+
+    @property
+    def capturable(self) -> bool:
+        # the process group's all-gather is issued from the host, after the replay
+        return not self.group.distributed or self.peer
+
+    def pre_reduce(self):
+        """Select and compact this rank's release (local launches, graph-capturable)."""
+        self.state.select(self.flat.grad)
+
+    def reduce(self, factorized: bool = False) -> float:
+        """``factorized``: :meth:`pre_reduce` already ran (inside the captured step)."""
+        if not factorized:
+            self.pre_reduce()
+        g, st, grad = self.group, self.state, self.flat.grad
+        W = g.world if g.distributed else 1
+        if not g.distributed:
+            st.combine(1, grad, st.send)
+        else:
+            gathered = st.gather_buffer(W)
+            if self.peer:
+                self._peer_gather().run(st.send, gathered, 2 * self.k)
+            else:
+                g.all_gather_into(gathered, st.send)
+            st.combine(W, grad, gathered)
+        self.comm_bytes = 8 * self.k
+        self.last_scale = 1.0 / W
+        return self.last_scale
+
+    def state_dict(self):
+        return self.state.state_dict()
+
+    def load_state_dict(self, sd):
+        self.state.load_state_dict(sd)
+
+    # file transport: one round, the downlink is the sparse union (at most W k pairs)
+    def payload(self):
+        self.pre_reduce()
+        st = self.state
+        return {"idx": st.idx.clone(), "val": st.val.clone(),
+                "n": torch.tensor(st.n, dtype=torch.int64)}
+
+    @classmethod
+    def aggregate(cls, payloads, cfg=None):
+        n = int(payloads[0]["n"])
+        out = torch.zeros(n, dtype=torch.float32)
+        hit = torch.zeros(n, dtype=torch.bool)
+        for p in payloads:  # site order: out[i] = ((+0 + v_0) + v_1) + ...
+            idx = p["idx"].cpu().to(torch.int64)
+            out[idx] = out[idx] + p["val"].cpu().float()
+            hit[idx] = True
+        idx = hit.nonzero().reshape(-1)
+        return {"idx": idx.to(torch.int32), "val": out[idx],
+                "n": torch.tensor(n, dtype=torch.int64),
+                "sites": torch.tensor(len(payloads), dtype=torch.int64)}
+
+    def apply(self, agg):
+        grad = self.flat.grad
+        if int(agg["n"]) != grad.numel():
+            raise ValueError(f"topK apply(): an aggregate of {grad.numel()} elements is "
+                             f"required, got {int(agg['n'])}")
+        grad.zero_()
+        grad[agg["idx"].to(grad.device, torch.int64)] = agg["val"].to(grad.device, torch.float32)
+        self.last_scale = 1.0 / int(agg["sites"])
+        return self.last_scale
+
+
+ENGINES = {"dSGD": DSGDEngine, "rankDAD": RankDADEngine, "powerSGD": PowerSGDEngine,
+           "topK": TopKEngine}
 
 
 def make_engine(name: str, model: nn.Module, flat: FlatParams, group: SiteGroup, cfg: dict) -> Engine:
@@ -1266,8 +1405,8 @@ def make_engine(name: str, model: nn.Module, flat: FlatParams, group: SiteGroup,
         raise ValueError(f"unknown agg_engine {name!r}; expected one of {sorted(ENGINES)}")
     if not cls.supports_dp and dp_options(dict(cfg or {}))[0] > 0:
         raise ValueError(f"dp_clip_norm: the private gradient release is implemented for dSGD "
-                         f"only, not agg_engine {name!r} (it shares factors, not a gradient)")
+                         f"only, not agg_engine {name!r} (it shares {cls.releases})")
     if not cls.supports_secure_agg and secure_agg_option(dict(cfg or {})):
         raise ValueError(f"secure_agg: the masked gradient sum is implemented for dSGD only, "
-                         f"not agg_engine {name!r} (it shares factors, not a gradient)")
+                         f"not agg_engine {name!r} (it shares {cls.releases})")
     return cls(model, flat, group, cfg)

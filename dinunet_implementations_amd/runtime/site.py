@@ -747,6 +747,11 @@ class FederatedSite:
             if cal:  # dsgd_collective="calibrate": what was measured and chosen
                 logs["dsgd_collective"] = cal
                 self.log(f"dsgd_collective calibrated: {cal}")
+            if engine.name == "topK":  # what every rank releases per step, and how it travels
+                logs["topk_ratio"], logs["topk_k"] = engine.ratio, engine.k
+                logs["topk_exchange"] = engine.transport
+                self.log(f"topK: k = {engine.k} of {trainer.flat.grad.numel()} elements, "
+                         f"exchange: {engine.transport}")
             if resume is not None:
                 if resume.get("engine"):
                     engine.load_state_dict(resume["engine"])

@@ -40,7 +40,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--effect", "--signal", dest="signal", type=float, default=0.6,
                     help="class-signal amplitude (--effect under torchrun: --signal is ambiguous there)")
-    ap.add_argument("--engine", default="dSGD", choices=["dSGD", "rankDAD", "powerSGD"])
+    ap.add_argument("--engine", default="dSGD", choices=["dSGD", "rankDAD", "powerSGD", "topK"])
     ap.add_argument("--cohort", default="easy", choices=["easy", "hard"])
     ap.add_argument("--label-noise", type=float, default=0.1, help="hard cohort")
     ap.add_argument("--compute-path", default="fused", choices=["fused", "reference"])

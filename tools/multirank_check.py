@@ -22,7 +22,12 @@ precision costs after Adam (which turns the sign of every near-zero mean gradien
 gradient is also compared with the oracle's (``grad_rel_err``, bounded by ``--grad-tol``): the
 payload's own error for dSGD, and for rank-dAD / PowerSGD the distance between the engine's
 reconstruction and the fp64 replay of the same factorisation.  (Bit-identical replicas alone would also pass if every rank applied the same
-WRONG update.)
+WRONG update.)  For ``topK`` the selection is exact integer logic, so no tolerance applies: every
+rank records the local gradient of its first step, rank 0 replays the numpy mirror
+(``ops.reference.topk_select`` / ``topk_combine``) from them and the first reduced gradient must
+match BIT FOR BIT (``grad_bit_exact``; that alone decides ``oracle_ok``).  The multi-step replay
+from recomputed gradients is reported for information: a last-bit difference in a recomputed
+gradient can move an element across the selection threshold.
 """
 import argparse
 import json
@@ -52,12 +57,28 @@ def oracle_reducer(engine, model, flat, cfg, world, dev):
       (P = orth(G_s Q); Q = G_s^T P; the last Q warm-starts its next step) and the layer
       gradient is mean_s P_s Q_s^T; every other parameter is the dSGD mean.
     * PowerSGD (Vogels et al. 2019, warm start): M_s = G_s + e_s; P = orth(mean_s M_s Q);
-      Q = mean_s M_s^T P (the next warm start); G = P Q^T; e_s = M_s - G; vectors: mean."""
+      Q = mean_s M_s^T P (the next warm start); G = P Q^T; e_s = M_s - G; vectors: mean.
+    * topK: the numpy mirror with one residual per site; the sum of the pairs over W."""
     import torch
     from dinunet_implementations_amd.parallel import make_engine
     from dinunet_implementations_amd.parallel.group import SiteGroup
     if engine == "dSGD":
         return lambda gs: sum(gs) / len(gs)
+    if engine == "topK":
+        import numpy as np
+        from dinunet_implementations_amd.ops import reference as ref
+        n = flat.grad.numel()
+        k = ref.topk_k(n, float(cfg.get("topk_ratio", 0.01)))
+        errs = [np.zeros(n, dtype=np.float32) for _ in range(world)]
+
+        def red(gs):
+            pairs = []
+            for s, gsite in enumerate(gs):
+                idx, val, errs[s] = ref.topk_select(gsite.float(), errs[s], k)
+                pairs.append((idx, val))
+            out = torch.from_numpy(ref.topk_combine(pairs, n)).to(dev)
+            return out.double() / len(gs)
+        return red
     tmpl = make_engine(engine, model, flat, SiteGroup(device=dev), dict(cfg))  # initial state
     seg = {id(p): (o, n) for p, o, n in flat.segments()}
     if engine == "rankDAD":
@@ -127,6 +148,7 @@ def main():
                     help="dsgd_collective (auto | direct | allreduce | peer | calibrate)")
     ap.add_argument("--dad-tol", type=float, default=None,
                     help="dad_tol (the rank-dAD oracle replays a fixed iteration count: pass 0)")
+    ap.add_argument("--topk-ratio", type=float, default=0.01)
     ap.add_argument("--grad-tol", type=float, default=None,
                     help="bound on the first step's reduced-gradient error vs the fp64 oracle "
                          "(dSGD; default: 1e-6 at 32 bits, 2e-3 at 16)")
@@ -150,12 +172,22 @@ def main():
     init = flat.data.detach().clone()
     opt = FusedAdam(flat, lr=1e-3)
     cfg = {"precision_bits": a.precision, "dad_reduction_rank": 8, "powersgd_rank": 4, "seed": 5,
-           "dsgd_overlap": bool(a.overlap), "dsgd_collective": a.collective}
+           "dsgd_overlap": bool(a.overlap), "dsgd_collective": a.collective,
+           "topk_ratio": a.topk_ratio}
     if a.payload:
         cfg["payload_dtype"] = a.payload
     if a.dad_tol is not None:
         cfg["dad_tol"] = a.dad_tol
     eng = make_engine(a.engine, m, flat, grp, cfg)
+    local_first = []  # topK: this rank's local gradient of the first release
+    if a.engine == "topK":
+        select = eng.state.select
+
+        def recording_select(grad):
+            if not local_first:
+                local_first.append(grad.detach().clone())
+            return select(grad)
+        eng.state.select = recording_select
     counts = {}
     if a.diag and hasattr(eng, "_on_grad"):
         names = {id(p): n for n, p in m.named_parameters()}
@@ -186,7 +218,7 @@ def main():
             y = torch.randint(0, 2, (B,), device=dev, generator=g)
             yield i, x, y
 
-    g_first = None
+    g_first = g_first_raw = None
     if a.feed == "device":
         if a.ragged:
             raise SystemExit("--feed device does not take --ragged")
@@ -199,6 +231,7 @@ def main():
         step(x, y, first=i % a.accum == 0, last=i % a.accum == a.accum - 1)
         if i == a.accum - 1:  # the first reduced gradient (every engine writes it to flat.grad)
             g_first = (flat.grad.double() * getattr(eng, "last_scale", 1.0)).clone()
+            g_first_raw = flat.grad.detach().clone()
     if dev.type == "cuda":
         torch.cuda.synchronize()
     if getattr(eng, "peer", False):  # a timed-out wait of the peer exchange (sticky error words)
@@ -228,8 +261,12 @@ def main():
                v[2] is True for v in getattr(step, "_dgraphs", {}).values()
                if isinstance(v, tuple) and len(v) == 3)),
            "param_sum": float(mine.double().sum()), "peer_errors": errs}
+    if a.engine == "topK":
+        res["topk_k"], res["topk_exchange"] = eng.k, eng.transport
     if a.oracle:
         ok_o = torch.zeros(1, dtype=torch.float64, device=dev)
+        locals_ = (grp.all_gather(local_first[0].cpu()) if a.engine == "topK" and local_first
+                   else None)
         if grp.rank == 0:
             torch.manual_seed(1234)
             mo = ICALstm(input_size=128, hidden_size=384, num_comps=50, window_size=10).to(dev).train()
@@ -261,7 +298,20 @@ def main():
             res["update_max_abs_err"] = float((d_n - d_o).abs().max())
             res["update_norm"] = float(d_o.norm())
             good = err <= a.oracle_tol
-            if "grad_rel_err" in res:
+            if a.engine == "topK":
+                # the mirror fed with every rank's OWN first local gradient: the same bits
+                from dinunet_implementations_amd.ops import reference as ref
+                exact = False
+                if locals_ is not None and g_first_raw is not None:
+                    z = torch.zeros(flat.grad.numel()).numpy()
+                    want = ref.topk_combine([ref.topk_select(g, z, eng.k)[:2] for g in locals_],
+                                            flat.grad.numel())
+                    got = g_first_raw.cpu().numpy()
+                    exact = bool((got.view("uint32") == want.view("uint32")).all())
+                    res["grad_mismatches"] = int((got.view("uint32") != want.view("uint32")).sum())
+                res["grad_bit_exact"] = exact
+                good = exact
+            elif "grad_rel_err" in res:
                 gt = a.grad_tol if a.grad_tol is not None else (1e-6 if a.precision == "32" else 2e-3)
                 res["grad_tol"] = gt
                 good = good and res["grad_rel_err"] <= gt

@@ -31,6 +31,19 @@ __device__ __forceinline__ float dn_tanh(float x) {
   return 1.f - 2.f * dn_rcp(dn_exp2((2.f * DN_LOG2E) * x) + 1.f);
 }
 
+// ReLU as torch.relu: NaN stays NaN (fmaxf(NaN, 0) is 0, which hid a non-finite activation from
+// the gradient norm that skips the Adam step); a compare and a select, as cheap as the max
+__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
+
+// max(a, b) as torch.max: NaN if either is (fmaxf drops a NaN operand)
+__device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
+
+// One step of a running argmax as torch.argmax: does the candidate `v` replace the best so far?
+// NaN counts as the largest value and the first NaN stays (scan classes in ascending order).
+__device__ __forceinline__ bool argmax_takes(float v, float best) {
+  return v > best || (v != v && best == best);
+}
+
 __device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

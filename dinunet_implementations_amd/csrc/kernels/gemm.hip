@@ -295,10 +295,6 @@ __device__ __forceinline__ void group_bump(const GemmGroup& g) {
 
 typedef __attribute__((address_space(1))) unsigned gu32;
 
-// ReLU as torch.relu: NaN stays NaN (fmaxf(NaN, 0) is 0, which hid a non-finite activation from
-// the gradient norm that skips the Adam step); a compare and a select, as cheap as the max
-__device__ __forceinline__ float relu_f(float v) { return v < 0.f ? 0.f : v; }
-
 __device__ __forceinline__ void epi_store(const Epi& epi, void* C, long ldc, int row, int col, float v) {
   v *= epi.alpha;
   if (epi.bias) v += epi.bias[col];

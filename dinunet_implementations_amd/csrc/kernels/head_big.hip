@@ -277,7 +277,7 @@ headb_fwd_kernel(BArgs a, int l, const float* __restrict__ x, long ldx,
         for (int e = 0; e < 4; ++e) {
           const bool ok = gr < B && k + e < K;
           float y = sc[ok ? k + e : 0] * v[e] + sh[ok ? k + e : 0];
-          if (prelu) y = fmaxf(y, 0.f);
+          if (prelu) y = relu_f(y);
           v[e] = ok ? y : 0.f;
         }
       }
@@ -487,7 +487,7 @@ headb_loss_kernel(BArgs a, const long long* __restrict__ y, float* __restrict__ 
     int am = 0;
 #pragma unroll
     for (int c = 1; c < 16; ++c)
-      if (c < C && v[c] > mx) {
+      if (c < C && argmax_takes(v[c], mx)) {
         mx = v[c];
         am = c;
       }
@@ -800,7 +800,8 @@ headb_bwd_kernel(BArgs a, int l, char* __restrict__ ws, const float* __restrict_
         float v = acc[mt][r];
         if (pdrop > 0.f && v != 0.f) v = hkeep(seed, l, gr, k, K, pdrop) ? v * inv : 0.f;
         const float z = Zp[ok ? (long)gr * K + k : 0];
-        if (P.relu && s * z + t <= 0.f) v = 0.f;
+        // keep mask a > 0, as in mlp_head.hip and the GEMM mask epilogue: NaN is not kept
+        if (P.relu && !(s * z + t > 0.f)) v = 0.f;
         v = ok ? v : 0.f;
         if (P.bn) {
           if (ok) dyp[(long)gr * K + k] = v;

@@ -412,7 +412,7 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
         const int row = 16 * mt + 4 * q + r;
         float v = z[mt][r];
         if (L0.relu) {
-          v = fmaxf(v, 0.f);
+          v = relu_f(v);
           if (!(v > 0.f)) relu_ok &= ~(1u << (4 * mt + r));
         }
         v = (row < B && cv) ? v : 0.f;
@@ -499,7 +499,7 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
         for (int r = 0; r < 4; ++r) {
           const int row = 16 * mt + 4 * q + r;
           float v = z[mt][r];
-          if (L.relu) v = fmaxf(v, 0.f);
+          if (L.relu) v = relu_f(v);
           if (last) {
             logit[row * 16 + ln] = v;
           } else {
@@ -537,7 +537,7 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
     float mx = -INFINITY;
 #pragma unroll
     for (int cc = 0; cc < 16; ++cc)
-      if (cc < C) mx = fmaxf(mx, lg[cc]);
+      if (cc < C) mx = max_nan(mx, lg[cc]);
     float se = 0.f;
 #pragma unroll
     for (int cc = 0; cc < 16; ++cc)
@@ -594,7 +594,7 @@ head_rep_kernel(RepArgs a, const float* __restrict__ x, long ldx, const long lon
 #pragma unroll
       for (int cc = 0; cc < 16; ++cc) {
         if (cc < C) {
-          if (lg[cc] > amx) { amx = lg[cc]; am = cc; }
+          if (argmax_takes(lg[cc], amx)) { amx = lg[cc]; am = cc; }
           if (cc == yc) ly = lg[cc];
           if (mv) out[(long)m * C + cc] = a.log_out ? lg[cc] - lse : pr[cc];
         }

@@ -11,9 +11,11 @@ namespace {
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
   return v;
 }
+// equal for the argmax: the same value, or both NaN
+__device__ __forceinline__ bool same_rank(float a, float b) { return a == b || (a != a && b != b); }
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -51,25 +53,26 @@ softmax_xent_kernel(const float* __restrict__ z, const long* __restrict__ y, int
   for (int r = wid; r < B; r += 4) {
     const float* zr = z + (long)r * C;
     float mx = -INFINITY;
-    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, zr[c]);
+    for (int c = lane; c < C; c += 64) mx = max_nan(mx, zr[c]);
     mx = wave_max(mx);
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += __expf(zr[c] - mx);
     s = wave_sum(s);
     const float lse = mx + __logf(s);
     const long lab = y[r];
-    // argmax (first max index, like torch.max)
+    // argmax as torch.argmax: the first index of the largest value, NaN the largest of all.  A
+    // lane without a class keeps (-inf, INT_MAX) and loses every comparison to a lane with one.
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int c = lane; c < C; c += 64) {
       const float v = zr[c];
-      if (v > bv || (v == bv && c < bi)) { bv = v; bi = c; }
+      if (argmax_takes(v, bv) || (same_rank(v, bv) && c < bi)) { bv = v; bi = c; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o, 64);
       const int oi = __shfl_xor(bi, o, 64);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+      if (argmax_takes(ov, bv) || (same_rank(ov, bv) && oi < bi)) { bv = ov; bi = oi; }
     }
     if constexpr (LW) {
       const bool inr = lab >= 0 && lab < C;

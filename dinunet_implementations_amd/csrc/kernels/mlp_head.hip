@@ -265,7 +265,7 @@ __device__ __forceinline__ void fwd_epilogue(const HArgs& a, int l, const f32x4 
     for (int r = 0; r < 4; ++r) {
       const int row = 16 * mt + 4 * (lane >> 4) + r;
       float v = z[mt][r];
-      if (L.relu) v = fmaxf(v, 0.f);
+      if (L.relu) v = relu_f(v);
       if (last) {
         logit[row * 16 + (lane & 15)] = v;
       } else {
@@ -320,7 +320,7 @@ __device__ __forceinline__ void ln_fwd_stage(const HArgs& a, int l, int Mp, uint
       const float xh = ok ? ln_xhat(zr[c], mean, rstd) : 0.f;
       if (train) zr[c] = xh;
       float v = ok ? ln_y(L.gamma[cc], xh, L.beta[cc]) : 0.f;
-      if (L.relu) v = fmaxf(v, 0.f);
+      if (L.relu) v = relu_f(v);
       if (pn > 0.f && v != 0.f) v = hkeep(seed, l + 1, row, c, N, pn) ? v * invn : 0.f;
       const bf16 bv = (bf16)v;
       if (nxt) nxt[row * Sn + c] = bv;
@@ -679,7 +679,7 @@ __device__ __forceinline__ uint64_t fwd1_body(const HArgs& a, const float* __res
       int am = 0;
       for (int c = 0; c < C; ++c) {
         const float v = logit[m * 16 + c];
-        if (v > mx) { mx = v; am = c; }
+        if (argmax_takes(v, mx)) { mx = v; am = c; }
       }
       float se = 0.f;
       for (int c = 0; c < C; ++c) se += expf(logit[m * 16 + c] - mx);

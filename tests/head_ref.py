@@ -37,6 +37,15 @@ values BEFORE ``dZ`` is rounded (``bwd1_body``: ``sb += d`` ahead of the cast; `
 
 ``make_case`` rounds ``x`` and the weights to bf16 values once, for reference and baseline alike;
 biases, norm parameters and running statistics stay fp32.
+
+Non-finite values (``poison`` puts one into a case) follow torch in the forward: ``relu(NaN)`` is
+NaN, ``relu(-inf)`` is 0, a batch-statistics BatchNorm spreads a NaN over its column, LayerNorm and
+the softmax over its row, and ``argmax`` takes NaN for the largest value and returns the first one.
+The backward follows the mask rule the kernels declare, which is also that of the GEMM mask
+epilogue: the keep mask of a ReLU is ``a > 0``, a select and not a product, so a NaN activation is
+NOT kept and a gradient that meets a mask of zero is zero whatever it was.  torch autograd differs
+there (its ReLU backward is ``grad * (out > 0)``, a product, so a NaN gradient stays NaN where the
+mask is zero); ``tests/test_head_ref.py`` records where that shows and does not enforce it.
 """
 import collections
 import functools
@@ -191,6 +200,96 @@ def make_case(name, B, seed=None, loss_opts=False, off_grid=False):
                 class_weights=w, smoothing=eps or 0.0)
 
 
+POISON_WHERE = ("x", "W", "b", "gamma")
+
+
+def poison(case, where, value, l=0, i=0, k=0):
+    """A copy of ``case`` with one element replaced by ``value`` (``nan``, ``+inf``, ``-inf``):
+    ``x[i, k]``, or of layer ``l`` ``W[i, k]``, ``b[i]`` or ``gamma[i]``.  The case handed in is
+    left as it was."""
+    if where not in POISON_WHERE:
+        raise ValueError(where)
+    value = float(value)
+    c = dict(case, params=[dict(p) for p in case["params"]])
+    if where == "x":
+        t = case["x"].clone()
+        t[i, k] = value
+        c["x"] = t
+        return c
+    t = case["params"][l][where]
+    if t is None:
+        raise ValueError(f"layer {l} has no {where}")
+    t = t.clone()
+    if where == "W":
+        t[i, k] = value
+    else:
+        t[i] = value
+    c["params"][l][where] = t
+    return c
+
+
+NONFINITE_HEADS = ("ragged", "ica_ln", "ica", "fs")     # no norm, LayerNorm, running and batch BatchNorm
+EVAL_HEADS = ("ica", "ragged")                           # evaluation mode: running statistics, no norm
+
+
+def poison_case(name, B):
+    """The case the non-finite tests poison: ``make_case`` with dropout off.  (``ica_ln`` drops a
+    quarter of ``x``.  The kernels' dropout is a select, so a dropped NaN is gone, where torch's,
+    a product, keeps it; which element a seed drops is not what these tests are about.)"""
+    c = make_case(name, B)
+    return dict(c, layers=[L._replace(drop=0.0) for L in c["layers"]])
+
+
+def poisons(name, train=True):
+    """``(label, where, value, l, i, k)`` of every poison of a head: ``x[1, 3]`` and one weight of
+    the last layer with ``nan``, ``+inf`` and ``-inf``; one weight of layer 0, one hidden bias and
+    one norm ``gamma`` (where the head has them) with ``nan``."""
+    layers, _ = make_head(name)
+    last = len(layers) - 1
+    inf = math.inf
+    ps = [(f"x[1,3]={v}", "x", v, 0, 1, 3) for v in (math.nan, inf, -inf)]
+    ps.append(("W0[2,5]=nan", "W", math.nan, 0, 2, 5))
+    ps += [(f"W{last}[1,4]={v}", "W", v, last, 1, 4) for v in (math.nan, inf, -inf)]
+    hb = [l for l in range(last) if layers[l].bias]
+    if hb:
+        ps.append((f"b{hb[0]}[3]=nan", "b", math.nan, hb[0], 3, 0))
+    hn = [l for l in range(last) if layers[l].norm]
+    if hn:
+        ps.append((f"gamma{hn[0]}[2]=nan", "gamma", math.nan, hn[0], 2, 0))
+    return ps
+
+
+def nonfinite_matrix():
+    """``(head, train, poison label)`` of the non-finite tests."""
+    m = []
+    for h in NONFINITE_HEADS:
+        for train in (True, False) if h in EVAL_HEADS else (True,):
+            m += [(h, train, p[0]) for p in poisons(h)]
+    return m
+
+
+def poisoned(name, B, label):
+    """``(clean case, poisoned case, the poison)`` of one entry of ``nonfinite_matrix``."""
+    p = {q[0]: q for q in poisons(name)}[label]
+    c = poison_case(name, B)
+    return c, poison(c, p[1], p[2], p[3], p[4], p[5]), p
+
+
+def grad_tensors(case, g):
+    """``[(name, tensor)]`` of ``dx`` and every parameter gradient of ``backward``'s result."""
+    out = [("dx", g["dx"])]
+    for l in range(len(case["layers"])):
+        for k in ("gW", "gb", "ggamma", "gbeta"):
+            if g[k][l] is not None:
+                out.append((f"{k}{l}", g[k][l]))
+    return out
+
+
+def nonfinite(t):
+    """The set of non-finite elements of ``t`` as a boolean CPU tensor."""
+    return ~torch.isfinite(t.detach().to("cpu"))
+
+
 def modules(case, dtype=torch.float32, device="cpu"):
     """The plain ``torch.nn`` module list of a case (what ``ops.head.HeadSpec`` parses), with the
     case's parameters and running state loaded."""
@@ -243,7 +342,10 @@ def forward(case, dtype=torch.float64, rnd=NONE, masks=None, train=True, mm=torc
         own.append(m_own)
         V.append(v)
         m = masks[l] if masks is not None else m_own
-        a = _r(v if m is None else v * _t(m, dtype), rnd.a)
+        if masks is None and relu_below:
+            a = _r(torch.relu(v), rnd.a)     # (not v * m_own: NaN stays NaN, -inf becomes 0)
+        else:
+            a = _r(v if m is None else v * _t(m, dtype), rnd.a)
         W = _r(_t(p["W"], dtype), rnd.w)
         z = mm(a, W.t())
         if L.bias:
@@ -335,7 +437,7 @@ def backward(fw, dloss=1.0, mutate=None):
             m = _t(m, dtype)
             if mutate == "drop_no_scale" and L.drop:
                 m = (m != 0).to(dtype)
-            dA = dA * m
+            dA = torch.where(m != 0, dA * m, torch.zeros_like(dA))    # a select: see the docstring
         if l == 0:
             if mutate == "dx_last8":
                 dA = dA.clone()

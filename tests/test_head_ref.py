@@ -185,6 +185,122 @@ def test_dropout_masks_match_autograd(name):
 
 
 # ---------------------------------------------------------------------------------------------
+# non-finite values
+
+def _poisoned_chain(case, train):
+    """The poisoned case through the plain modules in fp64 with autograd (training) on."""
+    mods = [m for m in ref.modules(case, F64) if not isinstance(m, nn.Dropout)]
+    for m in mods:
+        m.train(train)
+    x = case["x"].double().requires_grad_(train)
+    with torch.set_grad_enabled(train):
+        logits = nn.Sequential(*mods)(x)
+        out, loss, _ = _loss_fn(case)(logits)
+    g = None
+    if train:
+        loss.backward()
+        lins = [m for m in mods if isinstance(m, nn.Linear)]
+        n = len(lins)
+        g = dict(dx=x.grad, gW=[m.weight.grad for m in lins],
+                 gb=[m.bias.grad if m.bias is not None else None for m in lins],
+                 ggamma=[None] * n, gbeta=[None] * n)
+        norms = iter(m for m in mods if isinstance(m, (nn.BatchNorm1d, nn.LayerNorm)))
+        for l, L in enumerate(case["layers"]):
+            if L.norm:
+                nm = next(norms)
+                g["ggamma"][l], g["gbeta"][l] = nm.weight.grad, nm.bias.grad
+    state = [(m.running_mean, m.running_var) for m in mods
+             if isinstance(m, nn.BatchNorm1d) and m.track_running_stats]
+    return logits.detach(), out.detach(), loss.detach(), g, state
+
+
+def test_poison_leaves_the_case_alone():
+    case = ref.poison_case("ica", 5)
+    before = [case["x"].clone()] + [p["W"].clone() for p in case["params"]]
+    for _, where, v, l, i, k in ref.poisons("ica"):
+        c = ref.poison(case, where, v, l, i, k)
+        t = c["x"] if where == "x" else c["params"][l][where]
+        assert int(ref.nonfinite(t).sum()) == 1
+        got = t[i, k] if t.dim() == 2 else t[i]
+        assert math.isnan(v) and math.isnan(float(got)) or float(got) == v
+    for a, b in zip(before, [case["x"]] + [p["W"] for p in case["params"]]):
+        assert torch.equal(a, b)
+    assert all(bool(torch.isfinite(p[k]).all()) for p in case["params"] for k in p
+               if p[k] is not None)
+    with pytest.raises(ValueError):
+        ref.poison(ref.poison_case("ragged", 5), "gamma", math.nan)
+
+
+@pytest.mark.parametrize("name,train,label", ref.nonfinite_matrix())
+def test_poisoned_forward_matches_the_modules(name, train, label):
+    """Where a NaN or an infinity goes in the reference's forward is where torch's modules take
+    it: the same non-finite elements of ``out``, ``loss`` and the new running statistics;
+    ``pred`` is the argmax of the logits the chain ends in (NaN the largest, the first one wins),
+    which on every row whose ``out`` is finite is the argmax of ``out`` as well (a row of ``out``
+    with a NaN logit is all NaN: its argmax, 0, says nothing)."""
+    for B in (5, 17):
+        clean, case, _ = ref.poisoned(name, B, label)
+        logits, out, loss, _, state = _poisoned_chain(case, train)
+        fw = ref.forward(case, F64, ref.NONE, train=train)
+        assert torch.equal(ref.nonfinite(fw["logits"]), ref.nonfinite(logits))
+        assert torch.equal(ref.nonfinite(fw["out"]), ref.nonfinite(out))
+        assert bool(ref.nonfinite(fw["loss"])) == bool(ref.nonfinite(loss))
+        assert bool(ref.nonfinite(loss)), "every poison of the matrix reaches the loss"
+        assert torch.equal(fw["pred"], logits.argmax(1))
+        ok = torch.isfinite(out).all(1)
+        assert torch.equal(fw["pred"][ok], out.argmax(1)[ok])
+        if train:
+            got = [(a, b) for a, b in zip(fw["rmean"], fw["rvar"]) if a is not None]
+            assert len(got) == len(state)
+            for (a, b), (c, d) in zip(got, state):
+                assert torch.equal(ref.nonfinite(a), ref.nonfinite(c))
+                assert torch.equal(ref.nonfinite(b), ref.nonfinite(d))
+        if not train and label.startswith("x"):     # finite statistics: only the poisoned row
+            bad = ref.nonfinite(fw["out"]).any(1)
+            assert bad.tolist() == [r == 1 for r in range(B)]
+            assert torch.equal(fw["out"][~bad], ref.forward(clean, F64, train=False)["out"][~bad])
+
+
+@pytest.mark.parametrize("name,train,label",
+                         [c for c in ref.nonfinite_matrix() if c[1]])
+def test_poisoned_backward_follows_the_declared_mask_rule(name, train, label, record_property):
+    """The backward keeps ``a > 0`` by a select, so it can only have FEWER non-finite gradients
+    than autograd, whose ReLU backward passes the gradient on at a NaN output: the reference's
+    non-finite set of every tensor is inside autograd's, the tensors where it is smaller are
+    recorded (not enforced), and a non-finite loss still leaves a non-finite parameter gradient."""
+    B = 17
+    _, case, _ = ref.poisoned(name, B, label)
+    _, _, loss, g_auto, _ = _poisoned_chain(case, True)
+    fw = ref.forward(case, F64, ref.NONE)
+    g = ref.backward(fw)
+    differ = []
+    for (n, a), (_, b) in zip(ref.grad_tensors(case, g), ref.grad_tensors(case, g_auto)):
+        na, nb = ref.nonfinite(a), ref.nonfinite(b)
+        assert bool((nb | ~na).all()), n
+        if not torch.equal(na, nb):
+            differ.append(n)
+    print(f"{name} {label}: declared rule and autograd differ in {differ}")
+    record_property("differ", ",".join(differ))
+    assert bool(ref.nonfinite(loss))
+    assert any(bool(ref.nonfinite(t).any()) for n, t in ref.grad_tensors(case, g) if n != "dx")
+
+
+def test_relu_and_argmax_of_the_reference_keep_a_nan():
+    """The two places a plain formula loses one: ``v * (v > 0)`` is NaN for ``-inf`` and
+    ``max`` / ``argmax`` written with comparisons skip a NaN."""
+    case = ref.poison_case("ragged", 5)
+    c = ref.poison(case, "x", -math.inf, i=1, k=3)
+    fw = ref.forward(c, F64)
+    z0 = fw["Z"][0][1]
+    assert bool((z0 == -math.inf).any()) and bool((z0 == math.inf).any())
+    a1 = fw["A"][1][1]
+    assert torch.equal(a1 == 0, z0 == -math.inf) and not bool(torch.isnan(a1).any())
+    c = ref.poison(case, "b", math.nan, l=2, i=3)
+    fw = ref.forward(c, F64)
+    assert fw["pred"].tolist() == [3] * 5 and bool(torch.isnan(fw["loss"]))
+
+
+# ---------------------------------------------------------------------------------------------
 # roundings and accumulation order
 
 @pytest.mark.parametrize("switch", ref.Rounding._fields)

@@ -31,6 +31,14 @@
 // The mean sub-block uses the smallest of its W exponents (|mean| <= max |g_w|, so it cannot
 // overflow).  bf16 / fp32 sub-blocks carry e = 0 (their exponent range is fp32's).
 //
+// e is clamped to [-113, 100].  -113 covers all of fp32 (max |g| < 2^128 gives e >= -113, and
+// 2^113 and 2^-113 are normal fp32, so un-scaling stays exact); clamped at -100, as it once was,
+// a sub-block with max |g| >= 2^116 went out as inf.  The upper clamp only costs precision where
+// max |g| < 2^-85: there the sub-block is scaled by 2^100 and its values sink into fp16's
+// subnormals.  What the format does not cover: the W site values are summed in fp32 before the
+// division by W, so sum_w |g_w| has to stay below 2^128, and a sub-block holding an inf or a NaN
+// goes out unscaled (e = 0), its finite elements with fp16's own range.
+//
 // Layout: a rank-block of `chunk` elements (a multiple of SB) is chunk / SB sub-blocks of
 // [HDR | SB]; the payload of W ranks is W rank-blocks back to back.
 //
@@ -88,13 +96,14 @@ constexpr int HDR = 8;     // header elements per sub-block (16 B at 16 bits)
 constexpr int SB = 2048;   // elements per scaled sub-block: 256 lanes x 8
 constexpr int SBS = HDR + SB;
 
-// block exponent of a range with max |x| = amax: max |x| * 2^e < 2^15
+// block exponent of a range with max |x| = amax: max |x| * 2^e < 2^15 for every finite fp32 amax
+// (e >= -113); amax < 2^-85 is scaled by 2^100 only
 __device__ __forceinline__ int scale_exp(float amax) {
   if (!(amax > 0.f) || !__builtin_isfinite(amax)) return 0;  // zero / inf / nan: unscaled
   int k;
   (void)__builtin_frexpf(amax, &k);  // amax = m * 2^k, m in [0.5, 1)
   const int e = 15 - k;
-  return e < -100 ? -100 : (e > 100 ? 100 : e);
+  return e < -113 ? -113 : (e > 100 ? 100 : e);
 }
 
 __device__ __forceinline__ float exp2i(int e) { return __builtin_ldexpf(1.f, e); }

@@ -99,12 +99,13 @@ __device__ __forceinline__ char* wptr(void* base, long elems) {
   return reinterpret_cast<char*>(base) + elems * (T == PT_F32 ? 4 : 2);
 }
 
+// as payload.hip: max |x| * 2^e < 2^15 over all of fp32 (e >= -113), e <= 100
 __device__ __forceinline__ int scale_exp(float amax) {
   if (!(amax > 0.f) || !__builtin_isfinite(amax)) return 0;
   int k;
   (void)__builtin_frexpf(amax, &k);
   const int e = 15 - k;
-  return e < -100 ? -100 : (e > 100 ? 100 : e);
+  return e < -113 ? -113 : (e > 100 ? 100 : e);
 }
 
 __device__ __forceinline__ float exp2i(int e) { return __builtin_ldexpf(1.f, e); }

@@ -62,11 +62,11 @@ def _code(dtype) -> int:
 
 
 def _scale_exp(amax: float) -> int:
-    """max|x| * 2^e < 2^15 (payload.hip scale_exp)."""
+    """max|x| * 2^e < 2^15 for every finite fp32 max (e >= -113; payload.hip scale_exp)."""
     if not (amax > 0.0) or amax == float("inf"):
         return 0
     e = 15 - math.frexp(amax)[1]
-    return max(-100, min(100, e))
+    return max(-113, min(100, e))
 
 
 def payload_numel(elems: int) -> int:

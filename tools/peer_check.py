@@ -10,6 +10,13 @@ captured HIP graph replayed several times with fresh data, and compare with an f
 Prints one JSON line (rank 0): per wire, the max relative error of the mean against fp64, whether
 every rank holds bit-identical means, the gather's exactness, and the device time per exchange.
 Exit status 0 iff every check passes.
+
+``--inputs FILE.npz`` replaces the random data and the fp64 tolerance by given vectors and an
+exact expectation: ``mean_<r>`` / ``gather_<r>`` are rank r's fp32 vectors, ``mean_<wire>`` and
+``gather_<wire>`` ([world, m]) the fp32 results expected on that wire (``tests/wire_ref.py`` writes
+them).  Mean and gather run once eagerly and once in a captured graph; every result is compared
+BIT FOR BIT (a position where both hold a NaN passes), and the line reports per wire the
+mismatch counts, whether every rank holds bit-identical results, and the error word.
 """
 import argparse
 import json
@@ -25,12 +32,76 @@ sys.path.insert(0, ROOT)
 TOL = {"fp32": 1e-6, "bf16": 1.6e-2, "fp16": 2e-3}
 
 
+def _mismatches(got, want):
+    """Positions where two fp32 tensors differ in a bit and are not both NaN."""
+    import torch
+    got, want = got.reshape(-1), want.reshape(-1)
+    bad = got.view(torch.int32) != want.view(torch.int32)
+    return int((bad & ~(got.isnan() & want.isnan())).sum())
+
+
+def check_inputs(a, grp, peer, wires):
+    """The ``--inputs`` mode: given vectors, bit-exact expectations."""
+    import numpy as np
+    import torch
+    dev, W, me = grp.device, grp.world, grp.rank
+    z = np.load(a.inputs)
+    mine = torch.from_numpy(z[f"mean_{me}"]).to(dev)
+    gmine = torch.from_numpy(z[f"gather_{me}"]).to(dev)
+    n, m = mine.numel(), gmine.numel()
+    stride = -(-m // 8) * 8
+    res = {"world": W, "n": n, "m": m, "ok": True}
+    for wire in wires:
+        want = torch.from_numpy(z[f"mean_{wire}"])
+        gwant = torch.from_numpy(z[f"gather_{wire}"]).reshape(W, m)
+        pm = peer.mean(grp, dev, n, wire, ("inputs", wire))
+        pg = peer.gather(grp, dev, m, wire, ("inputs", wire))
+        x = torch.empty(n, dtype=torch.float32, device=dev)
+        gdst = torch.empty(W * stride, dtype=torch.float32, device=dev)
+        out = {"mean_mismatches": {}, "gather_mismatches": {}, "replicas_identical": True}
+
+        def judge(how):
+            got = x.cpu()
+            out["mean_mismatches"][how] = _mismatches(got, want)
+            out["gather_mismatches"][how] = _mismatches(
+                gdst.cpu().view(W, stride)[:, :m].contiguous(), gwant)
+            outs = grp.all_gather(got.view(torch.int32))
+            out["replicas_identical"] = out["replicas_identical"] and all(
+                torch.equal(t, outs[0]) for t in outs)
+
+        x.copy_(mine)
+        gdst.fill_(-7.0)
+        pm.run_(x)
+        pg.run(gmine, gdst, stride)
+        torch.cuda.synchronize()
+        judge("eager")
+        gr = torch.cuda.CUDAGraph()
+        grp.barrier()
+        with torch.cuda.graph(gr):
+            x.copy_(mine)
+            pm.run_(x)
+            pg.run(gmine, gdst, stride)
+        x.fill_(-7.0)
+        gdst.fill_(-7.0)
+        gr.replay()
+        torch.cuda.synchronize()
+        judge("graph")
+        out["error_word"] = pm.ar.error()
+        out["ok"] = (not any(out["mean_mismatches"].values()) and out["replicas_identical"]
+                     and not any(out["gather_mismatches"].values()) and out["error_word"] == 0)
+        res[wire] = out
+        res["ok"] = res["ok"] and out["ok"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--wire", default="all", help="fp32 | bf16 | fp16 | all")
     ap.add_argument("--n", type=int, default=1_063_106, help="elements (default: the ICA model)")
     ap.add_argument("--reps", type=int, default=4, help="graph replays with fresh data")
     ap.add_argument("--time", type=int, default=20, help="timed graph replays")
+    ap.add_argument("--inputs", default=None,
+                    help="npz of per-rank vectors and the fp32 results expected (bit-exact mode)")
     a = ap.parse_args()
 
     import torch
@@ -42,6 +113,9 @@ def main():
     W, me = grp.world, grp.rank
     wires = ["fp32", "bf16", "fp16"] if a.wire == "all" else [a.wire]
     res = {"world": W, "n": a.n, "ok": True}
+    if a.inputs:
+        res = check_inputs(a, grp, peer, wires)
+        wires = []
 
     def site_data(step, rank, n):
         g = torch.Generator(device="cpu").manual_seed(1000 * step + rank)

@@ -357,6 +357,8 @@ class RemoteNode:
                 self.rlogs["remote_iter_duration"].append(time.time() - t0)
                 return {"output": {"command": "powersgd_apply", "q_file": "agg_q.pt", "cfg": self.cfg}}
             agg = self.engine_cls.aggregate(pays, self.cfg)
+            if "trimmed" in agg:  # trimmedMean: which site was dropped how often (per epoch)
+                self._trim_add(agg.pop("trimmed"), int(agg["n"]), int(agg.pop("b")))
             _save(agg, os.path.join(tdir, "agg.pt"))
             self.rlogs["remote_iter_duration"].append(time.time() - t0)
             return self._after_step(apply_file="agg.pt")
@@ -381,6 +383,7 @@ class RemoteNode:
             stop = (self.best["wait"] >= int(self.cfg.get("patience", 10 ** 9))
                     or self.epoch >= int(self.cfg.get("epochs", 1)))
             self.rlogs["cumulative_total_duration"].append(time.time() - self.t_start)
+            self._trim_epoch()
             self.epoch += 1
             self.step = 0
             self.phase = "test" if stop else "train_after_decision"
@@ -428,6 +431,24 @@ class RemoteNode:
         self.phase = "init_fold"
         return {"output": {"command": "init_fold", "fold": self.fold, "seed": self.seed, "cfg": self.cfg}}
 
+    def _trim_add(self, counts, n: int, b: int):
+        """One trimmedMean aggregate's per-site trimmed-coordinate counts (site order)."""
+        acc = getattr(self, "_trim", None)
+        if acc is None:
+            acc = self._trim = {"counts": [0] * len(self.sites), "n": n, "reduces": 0}
+        acc["counts"] = [c + int(v) for c, v in zip(acc["counts"], counts.tolist())]
+        acc["reduces"] += 1
+
+    def _trim_epoch(self):
+        """``trimmed_share`` of the epoch that ends: counts / (n x reduces) per site."""
+        acc = getattr(self, "_trim", None)
+        if acc is None:
+            return
+        den = max(1, acc["n"] * acc["reduces"])
+        self.rlogs.setdefault("trimmed_share", []).append(
+            [round(c / den, 6) for c in acc["counts"]])
+        self._trim = None
+
     def _after_step(self, apply_file: Optional[str]):
         self.step += 1
         steps = max(self.steps_per_epoch, 1)
@@ -440,6 +461,7 @@ class RemoteNode:
                 return {"output": {"command": "validate", "apply_file": apply_file, "cfg": self.cfg}}
             last = self.epoch >= int(self.cfg.get("epochs", 1))
             self.rlogs["cumulative_total_duration"].append(time.time() - self.t_start)
+            self._trim_epoch()
             self.epoch += 1
             self.step = 0
             out = {"command": "train_round", "apply_file": apply_file, "cfg": self.cfg,

@@ -74,6 +74,9 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     # top-k sparsification (agg_engine "topK", ops.topk): the share of the gradient's elements a
     # rank releases per step, in (0, 1]; k = min(n, max(1, ceil(topk_ratio * n)))
     "topk_ratio": 0.01,
+    # coordinate-wise trimmed mean (agg_engine "trimmedMean", ops.trimmed): the sites dropped at
+    # each end of every coordinate's sorted values -- "median" ((W - 1) // 2) or an integer >= 0
+    "trim_sites": "median",
     # collective plan for the xGMI mesh (README "Collective plan"): dSGD bucket size, RCCL
     # algorithm / protocol (None = RCCL's own choice), per-collective timeout
     "dsgd_bucket_mb": 4.0,
@@ -397,7 +400,7 @@ def check_dp(cfg: Dict[str, Any]) -> None:
                          f"got {sd!r}")
 
 
-AGG_ENGINES = ("dSGD", "rankDAD", "powerSGD", "topK")
+AGG_ENGINES = ("dSGD", "rankDAD", "powerSGD", "topK", "trimmedMean")
 
 
 def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
@@ -409,6 +412,14 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
     if isinstance(tr, bool) or not isinstance(tr, (int, float)) or not (0 < tr <= 1):
         raise ValueError(f"topk_ratio must be a number in (0, 1], got {tr!r}")
     cfg["topk_ratio"] = tr
+    ts = cfg.get("trim_sites")
+    ts = "median" if ts is None else ts
+    if not (isinstance(ts, str) and ts == "median"):
+        if (isinstance(ts, bool) or not isinstance(ts, (int, float)) or not (0 <= ts < 2 ** 31)
+                or ts != int(ts)):
+            raise ValueError(f"trim_sites must be 'median' or an integer >= 0, got {ts!r}")
+        ts = int(ts)
+    cfg["trim_sites"] = ts
     if str(cfg.get("precision_bits")) not in ("16", "32"):
         raise ValueError("precision_bits must be '16' or '32'")
     cfg["precision_bits"] = str(cfg["precision_bits"])

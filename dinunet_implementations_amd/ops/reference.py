@@ -413,3 +413,64 @@ def topk_combine(pairs, n: int):
             idx = np.asarray(idx).astype(np.int64).reshape(-1)
             out[idx] = out[idx] + _f32(val)  # (one rank's indices are distinct)
     return out
+
+
+# ---- coordinate-wise trimmed mean / median over sites (csrc/kernels/trimmed.hip) -------------------
+def trimmed_b(W: int, trim="median") -> int:
+    """Sites dropped at each end of a coordinate's sorted values: ``trim`` itself, or for
+    ``"median"`` ``(W - 1) // 2`` (one value kept at odd ``W``, the two middle ones at even)."""
+    W = int(W)
+    return (W - 1) // 2 if trim == "median" else int(trim)
+
+
+def trimmed_inv(W: int, b: int):
+    """``float32(1) / float32(W - 2b)``: the host-made reciprocal every backend multiplies by."""
+    import numpy as np
+    return np.float32(1.0) / np.float32(int(W) - 2 * int(b))
+
+
+def trimmed_mean(rows, b: int):
+    """``(out fp32 [n], trimmed int64 [W])`` of the coordinate-wise trimmed mean of ``rows`` (fp32
+    ``[W, n]``, one row per site in rank order) with ``b`` sites dropped at each end,
+    ``0 <= 2b < W``.
+
+    Order: ``u = bits(x)``, ``key(x) = u ^ 0x80000000`` when the sign bit is clear, else ``~u``,
+    compared as unsigned 32-bit: the IEEE total order -NaN < -inf < ... < -0 < +0 < ... < +inf <
+    +NaN.  Per coordinate the ``W`` entries are sorted ascending by ``(key, site index)``: a
+    strict order that depends on the values alone.  Value: ``s = v[b]; s = s + v[b+1]; ...; s = s
+    + v[W-1-b]`` in fp32 in sorted order; ``out = s`` when ``m = W - 2b`` is 1, else ``s * inv``
+    with ``inv = float32(1) / float32(m)``: no division, no fused multiply-add.  Counts:
+    ``trimmed[w]`` is the number of coordinates at which site ``w`` sat at a sorted position ``<
+    b`` or ``>= W - b``.
+
+    Consequences: a NaN always sorts to an end, so with ``b >= 1`` up to ``b`` non-finite sites per
+    coordinate and sign never reach the update.  ``b = 0`` is a mean summed in VALUE order, not
+    site order: not bitwise dSGD.  The median is ``b = (W - 1) // 2``: one value at odd ``W``, the
+    mean of the two middle values at even ``W``.  ``W = 1`` is the identity (``b`` must be 0)."""
+    import numpy as np
+    if isinstance(rows, torch.Tensor):
+        rows = rows.detach().cpu().numpy()
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or rows.shape[0] < 1:
+        raise ValueError(f"trimmed_mean: rows must be [W, n], got {rows.shape}")
+    W, n = rows.shape
+    b = int(b)
+    if not (0 <= 2 * b < W):
+        raise ValueError(f"trimmed_mean: 0 <= 2b < W is required, got b = {b}, W = {W}")
+    u = rows.view(np.uint32)
+    key = np.where(u & np.uint32(0x80000000), ~u, u ^ np.uint32(0x80000000)).astype(np.uint64)
+    site = np.arange(W, dtype=np.uint64)[:, None]
+    # (key, site) as one word: 32 key bits above 32 site bits, so any W sorts the same way
+    word = np.sort((key << np.uint64(32)) | site, axis=0)
+    ssite = (word & np.uint64(0xFFFFFFFF)).astype(np.int64)
+    k32 = (word >> np.uint64(32)).astype(np.uint32)
+    vals = np.where(k32 & np.uint32(0x80000000), k32 ^ np.uint32(0x80000000),
+                    ~k32).astype(np.uint32).view(np.float32)
+    with np.errstate(all="ignore"):
+        s = vals[b].copy()
+        for p in range(b + 1, W - b):
+            s = s + vals[p]
+        out = s if W - 2 * b == 1 else s * trimmed_inv(W, b)
+    ends = np.concatenate([ssite[:b], ssite[W - b:]], axis=0).reshape(-1)
+    trimmed = np.bincount(ends, minlength=W).astype(np.int64)
+    return np.ascontiguousarray(out, dtype=np.float32), trimmed

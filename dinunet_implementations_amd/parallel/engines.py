@@ -1,5 +1,5 @@
-"""Gradient-aggregation engines: dSGD, rank-dAD, PowerSGD (reference ``comps/__init__.py:13-16``)
-and top-k sparsification.
+"""Gradient-aggregation engines: dSGD, rank-dAD, PowerSGD (reference ``comps/__init__.py:13-16``),
+top-k sparsification and the coordinate-wise trimmed mean.
 
 Each engine turns every site's local gradient (living in the flat grad buffer of
 ``ops.FlatParams``) into the *global* update all sites apply with their own optimizer, so
@@ -15,6 +15,9 @@ replicas stay identical:
 * ``topK``     magnitude top-k sparsification with per-rank error feedback: every rank releases
   the ``k = ceil(topk_ratio * n)`` largest entries of ``gradient + residual`` as (index, value)
   pairs, one all-gather, and every rank sums the pairs in rank order (``ops.topk``).
+* ``trimmedMean`` every site's dense gradient is gathered; per coordinate the ``trim_sites``
+  smallest and largest of the sites' values are dropped and the rest averaged (the median by
+  default), so one site's NaN or blown-up gradient does not reach the update (``ops.trimmed``).
 
 Every engine also exposes the three pieces the COINSTAC file transport needs
 (``payload`` on a site, ``aggregate`` on the remote, ``apply`` back on the site) with the same
@@ -40,6 +43,8 @@ from ..ops.dp import DPState
 from ..ops.optim import FlatParams
 from ..ops.secagg import SecAggState
 from ..ops.topk import FLOAT_INDEX_MAX, TopKState
+from ..ops.trimmed import MAX_SITES as TRIM_MAX_SITES
+from ..ops.trimmed import TrimmedState
 from .collective import (PAYLOAD_TYPES, SB, DirectMean, DirectSum, from_payload, launch_on,
                          payload_name, payload_numel, to_payload)
 from .group import SiteGroup
@@ -85,6 +90,19 @@ def topk_ratio_option(cfg: dict) -> float:
     if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0 < v <= 1):
         raise ValueError(f"topk_ratio must be a number in (0, 1], got {v!r}")
     return float(v)
+
+
+def trim_sites_option(cfg: dict):
+    """``trim_sites`` of ``cfg`` (default ``"median"``): the sites dropped at each end of every
+    coordinate's sorted values -- ``"median"`` or an integer >= 0."""
+    v = cfg.get("trim_sites")
+    v = "median" if v is None else v
+    if v == "median" and isinstance(v, str):
+        return v
+    if (isinstance(v, bool) or not isinstance(v, (int, float)) or not (0 <= v < 2 ** 31)
+            or v != int(v)):
+        raise ValueError(f"trim_sites must be 'median' or an integer >= 0, got {v!r}")
+    return int(v)
 
 
 _WARNED_TWO_PARTIES = False
@@ -1394,8 +1412,152 @@ class TopKEngine(Engine):
         return self.last_scale
 
 
+# =============================================================================================
+# coordinate-wise trimmed mean / median
+# =============================================================================================
+class TrimmedMeanEngine(Engine):
+    """Coordinate-wise trimmed mean over the sites (``ops.trimmed`` holds the contract): every
+    rank gathers every site's dense fp32 gradient and, per coordinate, drops the ``b`` smallest
+    and the ``b`` largest of the ``W`` values and averages the rest.  ``trim_sites`` gives ``b``;
+    ``"median"`` (the default) is ``b = (W - 1) // 2``.
+
+    A NaN sorts to an end, so with ``b >= 1`` up to ``b`` non-finite (or arbitrarily wrong) sites
+    per coordinate and sign never reach the update; the per-site counters say how often each site
+    was dropped.  It bounds each coordinate, nothing more: it is no privacy mechanism (every site
+    sees every site's gradient), and ``b = 0`` is a mean summed in value order.
+
+    The exchange is one all-gather of the ``n`` fp32 words per rank: inside the captured step
+    through the peer exchange (``dsgd_collective='peer'``), else host-issued through the process
+    group after the replay.  One site: the gradient is left as it is."""
+    name = "trimmedMean"
+    releases = "each site's dense gradient, compared coordinate by coordinate"
+
+    def __init__(self, model, flat, group, cfg=None):
+        super().__init__(model, flat, group, cfg)
+        if self.half:
+            raise ValueError(f"trimmedMean: the gradients travel as fp32; a {self.wire} payload "
+                             f"(precision_bits=16 / payload_dtype) is not implemented")
+        if group.replicas > 1:
+            raise ValueError(f"trimmedMean: {group.replicas} GPUs per site are not supported: a "
+                             f"site's replicas are not independent voters, and the site gradient "
+                             f"would have to be formed first")
+        self.trim = trim_sites_option(self.cfg)
+        grad = flat.grad
+        n = grad.numel()
+        g = group
+        W = g.world if g.distributed else 1
+        if W > TRIM_MAX_SITES:
+            raise ValueError(f"trimmedMean: at most {TRIM_MAX_SITES} sites, got {W}")
+        from ..ops import reference as _ref
+        # (one site on the file transport: the remote trims, over the payloads it receives)
+        self.b = _ref.trimmed_b(W, self.trim) if g.distributed else 0
+        if g.distributed and 2 * self.b >= W:
+            raise ValueError(f"trimmedMean: trim_sites = {self.b} drops {2 * self.b} of W = {W} "
+                             f"sites per coordinate and keeps none (2 * trim_sites < W is "
+                             f"required)")
+        # the combine runs on the device (csrc/kernels/trimmed.hip): the step may capture it
+        self.fast = bool(flat.data.is_cuda)
+        self.state = TrimmedState(grad.device, n, W, self.b)
+        self._logged = torch.zeros(W, dtype=torch.int64)  # counts already reported (site log)
+        if not g.distributed:
+            self.transport = "none (one site)"
+        elif self.peer:
+            self.transport = "peer gather (captured)"
+        else:
+            self.transport = "all-gather (host-issued)"
+        import logging
+        logging.getLogger(__name__).info("trimmedMean: W = %d sites, b = %d dropped at each end "
+                                         "(%s), exchange: %s", W, self.b, self.trim,
+                                         self.transport)
+        if g.distributed:
+            if self.state.stride != n:  # (FlatParams pads every segment: never with its buffer)
+                raise ValueError("trimmedMean: the flat gradient must hold a multiple of 4 "
+                                 "elements (the gathered rows are loaded 16 bytes at a time)")
+            self.state.gather_buffer()
+        if self.peer:  # the exchange region, built outside any capture (peer.PeerArena)
+            self._peer_gather()
+        self.last_scale = 1.0
+
+    def _peer_gather(self):
+        from . import peer as _peer
+        return _peer.gather(self.group, self.flat.grad.device, self.flat.grad.numel(), "fp32",
+                            (self.name, "grads"))
+
+    @property
+    def capturable(self) -> bool:
+        # the process group's all-gather is issued from the host, after the replay
+        return not self.group.distributed or self.peer
+
+    def reduce(self) -> float:
+        g, st, grad = self.group, self.state, self.flat.grad
+        if g.distributed:
+            rows = st.gather_buffer()  # [W, stride], stride == n
+            if self.peer:
+                self._peer_gather().run(grad, rows.view(-1), st.stride)
+            else:
+                g.all_gather_into(rows.view(-1), grad)
+            st.combine(rows, grad)
+        self.comm_bytes = 4 * grad.numel()
+        self.last_scale = 1.0  # the result is a mean already
+        return self.last_scale
+
+    def trimmed_share(self) -> List[float]:
+        """Each site's share of trimmed coordinates since the last call: counts delta / (n x
+        reduces).  Every reduce drops exactly ``2 b n`` entries, so the number of reduces is read
+        off the counters themselves (a replayed graph never passes through ``reduce()``)."""
+        now = self.state.counts()
+        d = now - self._logged
+        self._logged = now
+        total = int(d.sum())
+        if total <= 0:
+            return [0.0] * self.state.W
+        return [float(v) * 2 * self.b / total for v in d.tolist()]
+
+    def state_dict(self):
+        return self.state.state_dict()
+
+    def load_state_dict(self, sd):
+        self.state.load_state_dict(sd)
+        self._logged = self.state.counts()
+
+    # file transport: one round; the remote trims over the sites' payloads
+    def payload(self):
+        g = self.flat.grad
+        return {"grad": g.detach().clone(), "n": torch.tensor(g.numel(), dtype=torch.int64)}
+
+    @classmethod
+    def aggregate(cls, payloads, cfg=None):
+        from ..ops import reference as _ref
+        W, n = len(payloads), int(payloads[0]["n"])
+        b = _ref.trimmed_b(W, trim_sites_option(dict(cfg or {})))
+        if 2 * b >= W:
+            raise ValueError(f"trimmedMean: trim_sites = {b} drops {2 * b} of W = {W} sites per "
+                             f"coordinate and keeps none (2 * trim_sites < W is required)")
+        st = TrimmedState("cpu", n, W, b)
+        rows = st.gather_buffer()
+        for w, p in enumerate(payloads):  # site order
+            v = p["grad"].detach().cpu().reshape(-1)
+            if v.dtype != torch.float32 or v.numel() != n:
+                raise ValueError(f"trimmedMean aggregate(): {n} fp32 elements per site are "
+                                 f"required, site {w} sent {v.numel()} {v.dtype}")
+            rows[w, :n].copy_(v)
+        out = torch.empty(n, dtype=torch.float32)
+        st.combine(rows, out)
+        return {"grad": out, "n": torch.tensor(n, dtype=torch.int64), "trimmed": st.counts(),
+                "b": torch.tensor(b, dtype=torch.int64)}
+
+    def apply(self, agg):
+        grad = self.flat.grad
+        if int(agg["n"]) != grad.numel():
+            raise ValueError(f"trimmedMean apply(): an aggregate of {grad.numel()} elements is "
+                             f"required, got {int(agg['n'])}")
+        grad.copy_(agg["grad"].to(grad.device, torch.float32))
+        self.last_scale = 1.0
+        return self.last_scale
+
+
 ENGINES = {"dSGD": DSGDEngine, "rankDAD": RankDADEngine, "powerSGD": PowerSGDEngine,
-           "topK": TopKEngine}
+           "topK": TopKEngine, "trimmedMean": TrimmedMeanEngine}
 
 
 def make_engine(name: str, model: nn.Module, flat: FlatParams, group: SiteGroup, cfg: dict) -> Engine:

@@ -433,6 +433,13 @@ class FederatedSite:
                 logs.setdefault(f"{tag}ema_applied_decay", []).append(float(opt.applied_ema_decay))
             self._dp_log(engine, cfg, logs, tag)
             self._sa_log(engine, logs, tag)
+            if engine.name == "trimmedMean":
+                # each site's share of the epoch's coordinates at which it was dropped: the
+                # site that stands out is the outlier
+                share = [round(v, 6) for v in engine.trimmed_share()]
+                logs.setdefault(f"{tag}trimmed_share", []).append(share)
+                self.log(f"{tag}epoch {epoch} trimmedMean: share of coordinates trimmed per "
+                         f"site " + " ".join(f"{v:.4f}" for v in share))
             tl.append([round(avg.average, 6)] + met.get((monitor if monitor != "loss" else "auc",)))
             logs.setdefault(f"{tag}samples_per_sec", []).append(nsamp / dt if dt > 0 else 0.0)
             stop = False
@@ -752,6 +759,9 @@ class FederatedSite:
                 logs["topk_exchange"] = engine.transport
                 self.log(f"topK: k = {engine.k} of {trainer.flat.grad.numel()} elements, "
                          f"exchange: {engine.transport}")
+            if engine.name == "trimmedMean":  # the voters, the dropped, and how they travel
+                self.log(f"trimmedMean: W = {engine.state.W} sites, b = {engine.b} dropped at "
+                         f"each end of every coordinate, exchange: {engine.transport}")
             if resume is not None:
                 if resume.get("engine"):
                     engine.load_state_dict(resume["engine"])

@@ -27,7 +27,10 @@ rank records the local gradient of its first step, rank 0 replays the numpy mirr
 (``ops.reference.topk_select`` / ``topk_combine``) from them and the first reduced gradient must
 match BIT FOR BIT (``grad_bit_exact``; that alone decides ``oracle_ok``).  The multi-step replay
 from recomputed gradients is reported for information: a last-bit difference in a recomputed
-gradient can move an element across the selection threshold.
+gradient can move an element across the selection threshold.  ``trimmedMean`` (``--trim``) is
+judged the same way: the first reduced gradient against ``ops.reference.trimmed_mean`` fed with
+every rank's own local gradient, bit for bit, and the per-site counters after that step against
+the mirror's counts (``trimmed_counts_exact``); ``trim_exchange`` names the gather that ran.
 """
 import argparse
 import json
@@ -58,7 +61,8 @@ def oracle_reducer(engine, model, flat, cfg, world, dev):
       gradient is mean_s P_s Q_s^T; every other parameter is the dSGD mean.
     * PowerSGD (Vogels et al. 2019, warm start): M_s = G_s + e_s; P = orth(mean_s M_s Q);
       Q = mean_s M_s^T P (the next warm start); G = P Q^T; e_s = M_s - G; vectors: mean.
-    * topK: the numpy mirror with one residual per site; the sum of the pairs over W."""
+    * topK: the numpy mirror with one residual per site; the sum of the pairs over W.
+    * trimmedMean: the numpy mirror over the sites' fp32 gradients."""
     import torch
     from dinunet_implementations_amd.parallel import make_engine
     from dinunet_implementations_amd.parallel.group import SiteGroup
@@ -78,6 +82,15 @@ def oracle_reducer(engine, model, flat, cfg, world, dev):
                 pairs.append((idx, val))
             out = torch.from_numpy(ref.topk_combine(pairs, n)).to(dev)
             return out.double() / len(gs)
+        return red
+    if engine == "trimmedMean":
+        import numpy as np
+        from dinunet_implementations_amd.ops import reference as ref
+        b = ref.trimmed_b(world, cfg.get("trim_sites", "median"))
+
+        def red(gs):
+            rows = np.stack([gsite.float().cpu().numpy() for gsite in gs])
+            return torch.from_numpy(ref.trimmed_mean(rows, b)[0]).to(dev).double()
         return red
     tmpl = make_engine(engine, model, flat, SiteGroup(device=dev), dict(cfg))  # initial state
     seg = {id(p): (o, n) for p, o, n in flat.segments()}
@@ -149,6 +162,8 @@ def main():
     ap.add_argument("--dad-tol", type=float, default=None,
                     help="dad_tol (the rank-dAD oracle replays a fixed iteration count: pass 0)")
     ap.add_argument("--topk-ratio", type=float, default=0.01)
+    ap.add_argument("--trim", default="median",
+                    help="trim_sites (trimmedMean): 'median' or the sites dropped at each end")
     ap.add_argument("--grad-tol", type=float, default=None,
                     help="bound on the first step's reduced-gradient error vs the fp64 oracle "
                          "(dSGD; default: 1e-6 at 32 bits, 2e-3 at 16)")
@@ -173,7 +188,8 @@ def main():
     opt = FusedAdam(flat, lr=1e-3)
     cfg = {"precision_bits": a.precision, "dad_reduction_rank": 8, "powersgd_rank": 4, "seed": 5,
            "dsgd_overlap": bool(a.overlap), "dsgd_collective": a.collective,
-           "topk_ratio": a.topk_ratio}
+           "topk_ratio": a.topk_ratio,
+           "trim_sites": a.trim if a.trim == "median" else int(a.trim)}
     if a.payload:
         cfg["payload_dtype"] = a.payload
     if a.dad_tol is not None:
@@ -188,6 +204,15 @@ def main():
                 local_first.append(grad.detach().clone())
             return select(grad)
         eng.state.select = recording_select
+    counts_first = []  # trimmedMean: the per-site counters after the first reduction
+    if a.engine == "trimmedMean":
+        reduce = eng.reduce
+
+        def recording_reduce():
+            if not local_first:  # (the first step runs eagerly: these are computed values)
+                local_first.append(flat.grad.detach().clone())
+            return reduce()
+        eng.reduce = recording_reduce
     counts = {}
     if a.diag and hasattr(eng, "_on_grad"):
         names = {id(p): n for n, p in m.named_parameters()}
@@ -232,6 +257,8 @@ def main():
         if i == a.accum - 1:  # the first reduced gradient (every engine writes it to flat.grad)
             g_first = (flat.grad.double() * getattr(eng, "last_scale", 1.0)).clone()
             g_first_raw = flat.grad.detach().clone()
+            if a.engine == "trimmedMean":
+                counts_first.append(eng.state.counts())
     if dev.type == "cuda":
         torch.cuda.synchronize()
     if getattr(eng, "peer", False):  # a timed-out wait of the peer exchange (sticky error words)
@@ -263,10 +290,13 @@ def main():
            "param_sum": float(mine.double().sum()), "peer_errors": errs}
     if a.engine == "topK":
         res["topk_k"], res["topk_exchange"] = eng.k, eng.transport
+    if a.engine == "trimmedMean":
+        res["trim_sites"], res["trim_exchange"] = eng.b, eng.transport
+        res["trimmed_counts"] = eng.state.counts().tolist()
     if a.oracle:
         ok_o = torch.zeros(1, dtype=torch.float64, device=dev)
-        locals_ = (grp.all_gather(local_first[0].cpu()) if a.engine == "topK" and local_first
-                   else None)
+        locals_ = (grp.all_gather(local_first[0].cpu())
+                   if a.engine in ("topK", "trimmedMean") and local_first else None)
         if grp.rank == 0:
             torch.manual_seed(1234)
             mo = ICALstm(input_size=128, hidden_size=384, num_comps=50, window_size=10).to(dev).train()
@@ -311,6 +341,22 @@ def main():
                     res["grad_mismatches"] = int((got.view("uint32") != want.view("uint32")).sum())
                 res["grad_bit_exact"] = exact
                 good = exact
+            elif a.engine == "trimmedMean":
+                # the mirror fed with every rank's OWN first local gradient: the same bits, and
+                # the same per-site counts
+                import numpy as np
+                from dinunet_implementations_amd.ops import reference as ref
+                exact = counts_ok = False
+                if locals_ is not None and g_first_raw is not None and counts_first:
+                    want, trimmed = ref.trimmed_mean(np.stack([g.numpy() for g in locals_]),
+                                                     eng.b)
+                    got = g_first_raw.cpu().numpy()
+                    exact = bool((got.view("uint32") == want.view("uint32")).all())
+                    res["grad_mismatches"] = int((got.view("uint32") != want.view("uint32")).sum())
+                    counts_ok = counts_first[0].tolist() == trimmed.tolist()
+                    res["trimmed_counts_first"] = counts_first[0].tolist()
+                res["grad_bit_exact"], res["trimmed_counts_exact"] = exact, counts_ok
+                good = exact and counts_ok
             elif "grad_rel_err" in res:
                 gt = a.grad_tol if a.grad_tol is not None else (1e-6 if a.precision == "32" else 2e-3)
                 res["grad_tol"] = gt

@@ -70,6 +70,12 @@ class LocalNode:
             raise ValueError("class_weights='balanced' is computed by the in-process runtime "
                              "(runtime.site) from every site's label counts; the COINSTAC phase "
                              "machines need the explicit list of class weights")
+        if self.cfg.get("agg_engine") == "fedAvg":
+            # the phase machines send one payload per iteration; rounds every
+            # fedavg_local_steps updates need a cadence of their own over the file transport
+            raise ValueError("agg_engine 'fedAvg' (federated averaging with local steps) is "
+                             "implemented by the in-process runtime (runtime.site); the COINSTAC "
+                             "phase machines exchange a payload at every iteration")
         for c in (self.cfg, {**self.cfg, **(self.cfg.get("pretrain_args") or {})}):
             # the file transport ships engine.payload(), which the private release (issued by
             # DSGDEngine.reduce on the collective path) never sees

@@ -77,6 +77,15 @@ FRAMEWORK_DEFAULTS: Dict[str, Any] = {
     # coordinate-wise trimmed mean (agg_engine "trimmedMean", ops.trimmed): the sites dropped at
     # each end of every coordinate's sorted values -- "median" ((W - 1) // 2) or an integer >= 0
     "trim_sites": "median",
+    # federated averaging with local steps (agg_engine "fedAvg", ops.fedavg): every site takes
+    # fedavg_local_steps updates of its own between two rounds (4 is a design default, not a
+    # tuned value); a round averages the sites' parameter differences, "uniform" or weighted by
+    # the train-split "samples", and every site adopts anchor + fedavg_server_lr * (momentum of)
+    # the mean, with fedavg_server_momentum in [0, 1) (0 = none)
+    "fedavg_local_steps": 4,
+    "fedavg_weighting": "uniform",
+    "fedavg_server_lr": 1.0,
+    "fedavg_server_momentum": 0.0,
     # collective plan for the xGMI mesh (README "Collective plan"): dSGD bucket size, RCCL
     # algorithm / protocol (None = RCCL's own choice), per-collective timeout
     "dsgd_bucket_mb": 4.0,
@@ -400,7 +409,33 @@ def check_dp(cfg: Dict[str, Any]) -> None:
                          f"got {sd!r}")
 
 
-AGG_ENGINES = ("dSGD", "rankDAD", "powerSGD", "topK", "trimmedMean")
+AGG_ENGINES = ("dSGD", "rankDAD", "powerSGD", "topK", "trimmedMean", "fedAvg")
+
+FEDAVG_WEIGHTINGS = ("uniform", "samples")
+
+
+def check_fedavg(cfg: Dict[str, Any]) -> None:
+    """The federated-averaging keys of ``cfg`` (normalised in place)."""
+    k = cfg.get("fedavg_local_steps")
+    k = 4 if k is None else k
+    if not _is_int(k) or k < 1:
+        raise ValueError(f"fedavg_local_steps must be an integer >= 1, got {k!r}")
+    cfg["fedavg_local_steps"] = k
+    wt = cfg.get("fedavg_weighting")
+    wt = "uniform" if wt is None else wt
+    if not (isinstance(wt, str) and wt in FEDAVG_WEIGHTINGS):
+        raise ValueError(f"fedavg_weighting must be 'uniform' or 'samples', got {wt!r}")
+    cfg["fedavg_weighting"] = wt
+    lr = cfg.get("fedavg_server_lr")
+    lr = 1.0 if lr is None else lr
+    if not _is_num(lr) or not (0 < lr <= 3.4e38):
+        raise ValueError(f"fedavg_server_lr must be a finite number > 0, got {lr!r}")
+    cfg["fedavg_server_lr"] = lr
+    mo = cfg.get("fedavg_server_momentum")
+    mo = 0.0 if mo is None else mo
+    if not _is_num(mo) or not (0 <= mo < 1):
+        raise ValueError(f"fedavg_server_momentum must be a number in [0, 1), got {mo!r}")
+    cfg["fedavg_server_momentum"] = mo
 
 
 def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
@@ -420,6 +455,7 @@ def validate(cfg: Dict[str, Any]) -> Dict[str, Any]:
             raise ValueError(f"trim_sites must be 'median' or an integer >= 0, got {ts!r}")
         ts = int(ts)
     cfg["trim_sites"] = ts
+    check_fedavg(cfg)
     if str(cfg.get("precision_bits")) not in ("16", "32"):
         raise ValueError("precision_bits must be '16' or '32'")
     cfg["precision_bits"] = str(cfg["precision_bits"])
@@ -551,8 +587,8 @@ def generate_compspec() -> Dict[str, Any]:
             "id": "dinunet-mi355x",
             "version": "v0.1.0",
             "repository": "local",
-            "description": "FS-MLP / ICA-LSTM across sites with dSGD, rank-dAD, PowerSGD or "
-                           "top-k sparsification; "
+            "description": "FS-MLP / ICA-LSTM across sites with dSGD, rank-dAD, PowerSGD, "
+                           "top-k sparsification, a trimmed mean or federated averaging; "
                            "one MI355X per site, RCCL collectives over xGMI.",
         },
         "computation": {

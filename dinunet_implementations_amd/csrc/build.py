@@ -38,7 +38,11 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-ffp-contr
 # per-file code-generation flags: the low-rank kernels' fp64 / f32 MFMA accumulators stay in
 # VGPRs (the AGPR form made hipcc copy every loop-carried accumulator AGPR <-> VGPR each
 # iteration of the Gram loop: 19k -> see profiles/r2_lowrank_stamps.txt)
-FILE_FLAGS = {"lowrank.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+FILE_FLAGS = {"lowrank.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+              # the fedAvg round is specified operation by operation (a numpy float32 mirror gives
+              # its bits): no contraction.  hipcc's __fmul_rn / __fadd_rn are plain operators in
+              # its math header, which -ffp-contract=fast would still fuse
+              "fedavg.hip": ["-ffp-contract=off"]}
 
 
 def _sources(kind: str):

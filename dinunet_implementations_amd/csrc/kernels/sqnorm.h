@@ -14,21 +14,27 @@ __device__ __forceinline__ double wave_sum_f64(double x) {  // fixed butterfly: 
   return x;
 }
 
+// The 256 threads' accumulators of a workgroup summed in one fixed order into *slot (every thread
+// of the workgroup calls it).
+__device__ __forceinline__ void sqnorm_block_sum(double acc, double* __restrict__ slot) {
+  __shared__ double wsum[4];
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) *slot = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
 // Body of a <<<SQNORM_PARTS, 256>>> launch: part[blockIdx.x] = sum of g^2 over this workgroup's
 // grid-stride share of the n4 float4 of g.
 __device__ __forceinline__ void sqnorm_partial(const float* __restrict__ g, long n4,
                                                double* __restrict__ part) {
-  __shared__ double wsum[4];
   double acc = 0.0;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
     const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc += (double)gg[e] * (double)gg[e];
   }
-  acc = wave_sum_f64(acc);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+  sqnorm_block_sum(acc, part + blockIdx.x);
 }
 
 // The partials summed in one fixed order (all 64 lanes of the wave active; every lane gets the

@@ -11,6 +11,7 @@ from .dp import DPState
 from .secagg import SecAggState
 from .topk import TopKState
 from .trimmed import TrimmedState
+from .fedavg import FedAvgState
 from .heads import softmax_ce, log_softmax_nll
 from .head import HeadSpec, check_loss_options, head_loss
 from .layernorm import LayerNorm, layer_norm
@@ -25,6 +26,6 @@ def bilstm(x, params, reduce: str = "none", modules=None, packed=None, xp=None,
 __all__ = [
     "LayerNorm", "layer_norm",
     "mm", "linear_bias_relu", "bilstm", "lstm_supported", "padded_hidden", "FlatParams",
-    "DeviceSource", "StepRecorder", "FusedAdam", "DPState", "SecAggState", "TopKState", "TrimmedState", "LrSchedule", "cast_bf16_to_f32", "cast_f32_to_bf16", "step_prologue", "HeadSpec", "head_loss",
+    "DeviceSource", "StepRecorder", "FusedAdam", "DPState", "SecAggState", "TopKState", "TrimmedState", "FedAvgState", "LrSchedule", "cast_bf16_to_f32", "cast_f32_to_bf16", "step_prologue", "HeadSpec", "head_loss",
     "softmax_ce", "log_softmax_nll", "native_available", "capture", "reference",
 ]

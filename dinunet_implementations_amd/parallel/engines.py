@@ -1,5 +1,5 @@
 """Gradient-aggregation engines: dSGD, rank-dAD, PowerSGD (reference ``comps/__init__.py:13-16``),
-top-k sparsification and the coordinate-wise trimmed mean.
+top-k sparsification, the coordinate-wise trimmed mean, and federated averaging with local steps.
 
 Each engine turns every site's local gradient (living in the flat grad buffer of
 ``ops.FlatParams``) into the *global* update all sites apply with their own optimizer, so
@@ -18,6 +18,8 @@ replicas stay identical:
 * ``trimmedMean`` every site's dense gradient is gathered; per coordinate the ``trim_sites``
   smallest and largest of the sites' values are dropped and the rest averaged (the median by
   default), so one site's NaN or blown-up gradient does not reach the update (``ops.trimmed``).
+* ``fedAvg``   the one engine that does not exchange at every update: ``fedavg_local_steps``
+  one-site updates per site, then one mean of the sites' parameter differences (``ops.fedavg``).
 
 Every engine also exposes the three pieces the COINSTAC file transport needs
 (``payload`` on a site, ``aggregate`` on the remote, ``apply`` back on the site) with the same
@@ -40,6 +42,7 @@ from ..ops import _grad as _gradreg
 from ..ops import _lib
 from ..ops import capture as _cap
 from ..ops.dp import DPState
+from ..ops.fedavg import FedAvgState, site_weights
 from ..ops.optim import FlatParams
 from ..ops.secagg import SecAggState
 from ..ops.topk import FLOAT_INDEX_MAX, TopKState
@@ -1556,8 +1559,153 @@ class TrimmedMeanEngine(Engine):
         return self.last_scale
 
 
+# =============================================================================================
+# federated averaging with local steps
+# =============================================================================================
+class FedAvgEngine(Engine):
+    """FedAvg / local SGD (``ops.fedavg`` holds the contract of a round): every site takes
+    ``fedavg_local_steps`` updates of its own, then the sites average their parameter differences
+    from the model they last agreed on (the anchor) and adopt ``anchor + fedavg_server_lr * mean``
+    (through ``fedavg_server_momentum`` when it is on).
+
+    A local update is a one-site step: ``local`` -- a :class:`DSGDEngine` on a one-rank group --
+    is the engine the step and the device feed get, so the updates run the one-site step forms
+    unchanged (the update inside the captured K-step graph).  :meth:`round` runs between two of
+    them on the same stream: one delta launch, ONE site mean of the flat gradient buffer (any
+    wire, any collective, as every other mean), one adopt launch.  Adam's moments, BatchNorm
+    statistics and the step counter stay local to a site.
+
+    The site loop (``runtime.site``) calls :meth:`begin` where every site holds the same
+    parameters and :meth:`round` after every ``fedavg_local_steps``-th update of an epoch and
+    after its last, so validation and checkpoints see one model."""
+    name = "fedAvg"
+    releases = "parameter differences, not a gradient"
+
+    def __init__(self, model, flat, group, cfg=None):
+        super().__init__(model, flat, group, cfg)
+        from ..config import check_fedavg
+        opts = dict(self.cfg)
+        check_fedavg(opts)
+        if float(self.cfg.get("ema_decay") or os.environ.get("DINUNET_EMA_DECAY", "") or 0) > 0:
+            raise ValueError("fedAvg: ema_decay is not supported: every site would average the "
+                             "weights of its own local updates, so the averages that validation "
+                             "and test score would differ between the sites")
+        if group.replicas > 1:
+            raise ValueError(f"fedAvg: {group.replicas} GPUs per site are not supported: the "
+                             f"local updates are one-site steps, and a site's replicas would "
+                             f"have to exchange gradients at every one of them")
+        self.local_steps = int(opts["fedavg_local_steps"])
+        self.weighting = str(opts["fedavg_weighting"])
+        self.eta = float(opts["fedavg_server_lr"])
+        self.beta = float(opts["fedavg_server_momentum"])
+        # this site's weight: 1 ("uniform"), or set_samples() ("samples")
+        self.weight: Optional[float] = 1.0 if self.weighting == "uniform" else None
+        self.rounds = 0
+        self._restored = False
+        self.state = FedAvgState(flat, self.beta)
+        solo = SiteGroup(device=flat.data.device, outer=group if group.distributed else None)
+        self.local = DSGDEngine(model, flat, solo, self.cfg, overlap=False)
+        # the local updates run inside the captured step on the device path
+        self.fast = bool(flat.data.is_cuda)
+        if self.peer:  # the exchange region, built outside any capture (peer.PeerArena)
+            self._peer_mean(("round",), flat.grad.numel())
+
+    def set_samples(self, n_train: int):
+        """``fedavg_weighting="samples"``: all-gather the sites' train-split sizes and take this
+        site's weight ``fp32(W n_s / sum n)``; every site evaluates the same expression."""
+        if self.weighting != "samples":
+            return
+        sizes = self.group.all_gather_object(int(n_train))
+        self.weight = site_weights(sizes)[self.group.rank if self.group.distributed else 0]
+
+    # the local updates -------------------------------------------------------------------------
+    def step_context(self):
+        return self.local.step_context()
+
+    def reduce(self) -> float:
+        """A local update exchanges nothing."""
+        return self.local.reduce()
+
+    # rounds --------------------------------------------------------------------------------------
+    def begin(self):
+        """At a point where every site holds identical parameters (the start of a training phase,
+        after a resume): the anchor becomes the parameters; the momentum starts at zero unless a
+        checkpoint restored it."""
+        self.state.begin()
+        if self.state.u is not None and not self._restored:
+            self.state.u.zero_()
+        self._restored = False
+
+    def _weight(self) -> float:
+        if self.weight is None:
+            raise RuntimeError("fedAvg: fedavg_weighting='samples' needs set_samples() (the "
+                               "sites' train-split sizes) before the first round")
+        return self.weight
+
+    def round_due(self, update: int, steps: int) -> bool:
+        """Does a round follow the ``update``-th (1-based) of an epoch's ``steps`` updates?
+        Every ``fedavg_local_steps``-th and the last: ``ceil(steps / K)`` rounds per epoch."""
+        return update % self.local_steps == 0 or update == steps
+
+    def round(self):
+        """One round on the current stream: delta, the site mean, adopt.  One site is a world of
+        one: the mean is the site's own delta."""
+        st = self.state
+        st.delta(self._weight())
+        self._allreduce_mean_(self.flat.grad, tag=("round",))
+        st.adopt(self.eta, self.beta)
+        self.rounds += 1
+
+    @property
+    def drift(self) -> float:
+        """This site's ``||p - a||_2`` at the last round (a host read)."""
+        return float(self.state.drift)
+
+    def close(self):
+        self.local.close()
+
+    def state_dict(self):
+        # (an epoch ends with a round: at every checkpoint the anchor equals the parameters)
+        return {"rounds": int(self.rounds), **self.state.state_dict()}
+
+    def load_state_dict(self, sd):
+        self.rounds = int(sd.get("rounds", 0))
+        self.state.load_state_dict(sd)
+        self._restored = sd.get("u") is not None and self.state.u is not None
+
+    # file transport: one round; the phase machines' cadence of rounds is not implemented
+    # (compat/nodes.py refuses the engine), the pieces carry the collective path's arithmetic
+    def payload(self):
+        d = self.state.delta(self._weight())
+        out = {"delta": d.detach().clone()}
+        d.zero_()
+        return out
+
+    @classmethod
+    def aggregate(cls, payloads, cfg=None):
+        acc = None
+        for p in payloads:  # site order: (d_0 + d_1) + ...
+            v = p["delta"].detach().cpu().reshape(-1)
+            if v.dtype != torch.float32 or (acc is not None and v.numel() != acc.numel()):
+                raise ValueError("fedAvg aggregate(): fp32 deltas of one length are required")
+            acc = v.clone() if acc is None else acc.add_(v)
+        W = len(payloads)
+        return {"delta": acc if W == 1 else acc.mul_(torch.tensor(1.0 / W, dtype=torch.float32))}
+
+    def apply(self, agg):
+        grad = self.flat.grad
+        m = agg["delta"]
+        if m.numel() != grad.numel():
+            raise ValueError(f"fedAvg apply(): an aggregate of {grad.numel()} elements is "
+                             f"required, got {m.numel()}")
+        grad.copy_(m.to(grad.device, torch.float32).reshape(-1))
+        self.state.adopt(self.eta, self.beta)
+        self.rounds += 1
+        return 1.0
+
+
 ENGINES = {"dSGD": DSGDEngine, "rankDAD": RankDADEngine, "powerSGD": PowerSGDEngine,
-           "topK": TopKEngine, "trimmedMean": TrimmedMeanEngine}
+           "topK": TopKEngine, "trimmedMean": TrimmedMeanEngine, "fedAvg": FedAvgEngine}
 
 
 def make_engine(name: str, model: nn.Module, flat: FlatParams, group: SiteGroup, cfg: dict) -> Engine:

@@ -47,6 +47,9 @@ class SiteGroup:
     replicas: int = 1
     replica: int = 0
     site_pg: Any = None
+    # a solo group inside a distributed run (fedAvg's local updates): the sites' group, whose
+    # eager collectives must have retired before this group's step is captured
+    outer: Any = None
 
     @property
     def distributed(self) -> bool:

@@ -48,7 +48,8 @@ class DeviceFeed:
     predicted class, FS's hard-label scores)."""
 
     def __init__(self, step, X: torch.Tensor, Y: torch.Tensor, batch: int, nb: int,
-                 col: int = 1, steps_per_graph: Optional[int] = None):
+                 col: int = 1, steps_per_graph: Optional[int] = None,
+                 segment: Optional[int] = None):
         if not X.is_cuda:
             raise ValueError("DeviceFeed: the dataset must live on the GPU")
         self.step = step
@@ -67,20 +68,37 @@ class DeviceFeed:
         rows = torch.arange(self.nbb * self.B, device=X.device) % X.shape[0]
         self.src = DeviceSource(Xb, Y, self.B, order=rows)
         self.rec = StepRecorder(self.nbb, self.B, self.src.cursor, col=col)
-        K = steps_per_graph or default_graph_steps(self.nb)
+        # ``segment`` (fedAvg's ``fedavg_local_steps``): an epoch runs in segments of that many
+        # steps, the last one shorter (``run_epoch(after=...)``); a graph never spans two
+        self.segment = None if not segment else max(1, min(int(segment), self.nb))
+        K = steps_per_graph or default_graph_steps(self.segment or self.nb)
         step.bind(self.src, steps_per_graph=K, recorder=self.rec)
 
+    def segments(self):
+        """The step counts of an epoch's ``run`` calls: ``[nb]``, or with ``segment`` whole
+        segments and the remainder."""
+        if self.segment is None:
+            return [self.nb]
+        full, rest = divmod(self.nb, self.segment)
+        return [self.segment] * full + ([rest] if rest else [])
+
     # ---- epochs of the site loop --------------------------------------------------------------
-    def run_epoch(self, order: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def run_epoch(self, order: torch.Tensor, after=None
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Train ``nb`` steps on the batches ``order`` (``[nb * accum * batch]`` row indices, the
         epoch's batch sequence); returns the device tensors ``(losses [nb * accum], scores
-        [nb * accum * B], labels [nb * accum * B])`` of the epoch's per-batch train records."""
+        [nb * accum * B], labels [nb * accum * B])`` of the epoch's per-batch train records.
+        The order and the cursor are set once; ``after()`` is called after every segment's
+        ``run`` (fedAvg: the round, on the same stream)."""
         if order.numel() != self.nbb * self.B:
             raise ValueError(f"DeviceFeed.run_epoch: order of {order.numel()} rows, want "
                              f"{self.nbb * self.B}")
         self.src.set_order(order)
         self.src.cursor.zero_()
-        self.step.run(self.nb)
+        for n in self.segments():
+            self.step.run(n)
+            if after is not None:
+                after()
         return self.rec.losses, self.rec.scores.view(-1), self.src.labels_of(self.nbb)
 
     # ---- free-running steps (bench.py) --------------------------------------------------------
@@ -89,5 +107,11 @@ class DeviceFeed:
         return self.step.run(n)
 
     def prepare(self, n: int):
-        """Capture every graph a following :meth:`run` of ``n`` / :meth:`run_epoch` replays."""
-        self.step.prepare(n)
+        """Capture every graph a following :meth:`run` of ``n`` / :meth:`run_epoch` replays (with
+        ``segment``: those of a whole segment and of the epoch's remainder, so that a round
+        never waits on a capture)."""
+        if self.segment is None:
+            self.step.prepare(n)
+            return
+        for k in sorted(set(self.segments()), reverse=True):
+            self.step.prepare(k)

@@ -11,6 +11,8 @@ Phases per fold (``fold_0 .. fold_{k-1}``):
 3. training in lockstep: every site contributes a gradient at every step (``steps_per_epoch``
    = max over sites; sites with less data cycle their reshuffled loader), ``local_iterations``
    micro-batches per step, aggregation by the engine (dSGD / rank-dAD / PowerSGD), fused Adam.
+   ``fedAvg`` alone exchanges nothing at an update: its sites meet in a round after every
+   ``fedavg_local_steps``-th update of an epoch and after its last.
 4. every ``validation_epochs``: each site scores its validation split, scores+labels are
    all-gathered, the *global* metric (``monitor_metric``, ``metric_direction``) drives the
    best-epoch checkpoint and ``patience`` early stopping identically on every rank (the
@@ -323,16 +325,33 @@ class FederatedSite:
         # captures per-micro-batch activations (rank-dAD's CPU activation-space form)
         use_fast = trainer.has_fast_path and (li == 1 or getattr(engine, "fast", True)
                                                or engine.name != "rankDAD")
+        # fedAvg: the updates are one-site steps on the engine's solo dSGD engine; the sites meet
+        # in a round after every ``fedavg_local_steps``-th update of an epoch and after its last
+        fed = engine if engine.name == "fedAvg" else None
+        fed_k = fed.local_steps if fed is not None else 0
+        step_engine = fed.local if fed is not None else engine
+        if fed is not None:
+            fed.set_samples(tr.num_samples)
+            fed.begin()
+            if not logs.get(f"{tag}fedavg_local_steps"):
+                logs[f"{tag}fedavg_local_steps"] = fed.local_steps
+                logs[f"{tag}fedavg_weighting"] = fed.weighting
+                logs[f"{tag}fedavg_server_lr"] = fed.eta
+                logs[f"{tag}fedavg_server_momentum"] = fed.beta
+                self.log(f"fedAvg: a round after every {fed.local_steps} updates and at the end "
+                         f"of an epoch ({math.ceil(steps / fed.local_steps)} rounds per epoch), "
+                         f"weighting {fed.weighting} (this site {fed.weight:g}), server lr "
+                         f"{fed.eta:g}, momentum {fed.beta:g}")
         step = None
         if use_fast:
             use_graph = (bool(cfg.get("use_graph", True)) and self.device.type == "cuda"
                          and not trainer.reference_math)
             sm = trainer.split_module()
             if sm is not None:  # stem/body model: split capture overlaps the all-reduce
-                step = TrainStep(sm, trainer.flat, trainer.optimizer, engine, use_graph=use_graph,
-                                 accum=li)
+                step = TrainStep(sm, trainer.flat, trainer.optimizer, step_engine,
+                                 use_graph=use_graph, accum=li)
             else:
-                step = TrainStep(trainer.modules(), trainer.flat, trainer.optimizer, engine,
+                step = TrainStep(trainer.modules(), trainer.flat, trainer.optimizer, step_engine,
                                  use_graph=use_graph, accum=li,
                                  forward_loss=lambda m, x, y: trainer.forward_loss(x, y))
         opt = trainer.optimizer
@@ -345,7 +364,8 @@ class FederatedSite:
             # a fresh phase: the decay ends with its last update (a resumed one carries its own)
             opt.set_decay_steps(max(epochs * steps, opt.lr_schedule.warmup_steps + 1))
         fault_at = _fault_step(self.group.rank)
-        feed = self._device_feed(trainer, step, engine, tr, bs, li, steps, cfg, fault_at)
+        feed = self._device_feed(trainer, step, step_engine, tr, bs, li, steps, cfg, fault_at,
+                                 segment=fed_k)
         if resume and resume.get("loader"):
             it = tr.resume_iter(resume["loader"], indices=feed is not None)
         else:
@@ -367,6 +387,7 @@ class FederatedSite:
             t0 = time.time()
             avg, met = trainer.new_averages(), trainer.new_metrics()
             nsamp = 0
+            rounds0 = fed.rounds if fed is not None else 0
             if feed is not None:
                 # ONE host call per epoch: the epoch's batch order (the loader's own passes),
                 # then K-step graph replays with the train records kept on the device
@@ -377,11 +398,13 @@ class FederatedSite:
                     except StopIteration:
                         it = tr.iter_indices()
                         order.append(next(it))
-                losses, scores, labels = feed.run_epoch(torch.cat(order))
+                # (fedAvg: in segments of fedavg_local_steps updates, a round after each)
+                losses, scores, labels = feed.run_epoch(
+                    torch.cat(order), after=fed.round if fed is not None else None)
                 avg.add(losses.mean(), steps * li * bs)
                 met.add(scores.clone(), labels)
                 nsamp += steps * li * bs
-            for _ in range(steps if feed is None else 0):
+            for upd in range(1, (steps if feed is None else 0) + 1):
                 if fault_at is not None:  # failure-path tests (DINUNET_FAULT=<rank>:<step>)
                     fault_at -= 1
                     if fault_at < 0:
@@ -398,26 +421,30 @@ class FederatedSite:
                         # clone: a graph replay overwrites its static outputs next step
                         met.add(trainer.score(step.last_out, step.last_pred).detach().clone(), y)
                         nsamp += len(y)
+                    if fed is not None and fed.round_due(upd, steps):
+                        fed.round()
                     continue
                 trainer.flat.zero_grad()
-                if hasattr(engine, "sync_enabled"):
-                    engine.sync_enabled = False
-                with engine.step_context():
+                if hasattr(step_engine, "sync_enabled"):
+                    step_engine.sync_enabled = False
+                with step_engine.step_context():
                     for k in range(li):
                         try:
                             x, y, ix = next(it)
                         except StopIteration:
                             it = iter(tr)
                             x, y, ix = next(it)
-                        if hasattr(engine, "sync_enabled"):
-                            engine.sync_enabled = k == li - 1
+                        if hasattr(step_engine, "sync_enabled"):
+                            step_engine.sync_enabled = k == li - 1
                         out = trainer.iteration({"inputs": x, "labels": y, "ix": ix})
                         (out["loss"] / li).backward()
                         avg.accumulate(out["averages"])
                         met.accumulate(out["metrics"])
                         nsamp += len(y)
-                scale = engine.reduce()
+                scale = step_engine.reduce()
                 trainer.optimizer.step(grad_scale=scale)
+                if fed is not None and fed.round_due(upd, steps):
+                    fed.round()
             if self.device.type == "cuda":
                 torch.cuda.synchronize()
             dt = time.time() - t0
@@ -433,6 +460,11 @@ class FederatedSite:
                 logs.setdefault(f"{tag}ema_applied_decay", []).append(float(opt.applied_ema_decay))
             self._dp_log(engine, cfg, logs, tag)
             self._sa_log(engine, logs, tag)
+            if fed is not None:
+                # the epoch's rounds, and how far this site had moved from the last agreed
+                # model when the epoch's last round began
+                logs.setdefault(f"{tag}fedavg_rounds", []).append(fed.rounds - rounds0)
+                logs.setdefault(f"{tag}fedavg_drift", []).append(fed.drift)
             if engine.name == "trimmedMean":
                 # each site's share of the epoch's coordinates at which it was dropped: the
                 # site that stands out is the outlier
@@ -486,6 +518,7 @@ class FederatedSite:
                                         epoch=epoch, best=dict(best), logs=copy.deepcopy(logs),
                                         rng=trainer.rng_state(), loader=tr.state(),
                                         engine=engine.state_dict(), stopped=bool(stop))
+                # (fedAvg: an epoch ended with a round, so the anchor equals these parameters)
             if stop:
                 logs[f"{tag}stopped_epoch"] = epoch
                 break
@@ -563,7 +596,8 @@ class FederatedSite:
             "saturated": sa.saturated, "nonfinite": sa.nonfinite}
 
     def _device_feed(self, trainer: NNTrainer, step, engine, tr: DeviceLoader, bs: int, li: int,
-                     steps: int, cfg: Dict[str, Any], fault_at) -> Optional[DeviceFeed]:
+                     steps: int, cfg: Dict[str, Any], fault_at,
+                     segment: int = 0) -> Optional[DeviceFeed]:
         """The device-fed epoch (``runtime.feed``) when this site's step can take it: a captured
         step on the GPU, a model that takes a bf16 batch, a plugin with a score column, full
         batches, an engine that runs inside the captured step (``local_iterations`` > 1: whole
@@ -590,7 +624,8 @@ class FederatedSite:
                 self.log(f"device feed off: its copy of the train split ({need / 2**30:.2f} "
                          f"GiB) does not fit the free HBM ({free / 2**30:.2f} GiB)")
                 return None
-        return DeviceFeed(step, X, tr.labels, bs, steps, col=col)
+        # (``segment``, fedAvg: the epoch runs in segments of that many steps)
+        return DeviceFeed(step, X, tr.labels, bs, steps, col=col, segment=segment or None)
 
     def _pretrain(self, trainer: NNTrainer, data, fold_dir: str, seed: int, logs: Dict[str, Any],
                   fold: int = 0):

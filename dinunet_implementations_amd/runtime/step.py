@@ -78,7 +78,12 @@ def _quiesce_collectives(group) -> None:
     dsgd_collective=calibrate).  ``ProcessGroup._wait_for_pending_works`` returns once the
     watchdog's list is empty -- a condition, not a guessed delay (the round-5 form slept 0.3 s).
     ``init_sites`` also turns off torch's completion-event cache
-    (``TORCH_NCCL_CUDA_EVENT_CACHE=0``), so no pooled event is shared between works."""
+    (``TORCH_NCCL_CUDA_EVENT_CACHE=0``), so no pooled event is shared between works.
+    A solo group inside a distributed run (``SiteGroup.outer``, fedAvg: the rounds' collectives
+    are issued eagerly between the replays) waits for the sites' group."""
+    outer = getattr(group, "outer", None)
+    if outer is not None:
+        _quiesce_collectives(outer)
     if getattr(group, "distributed", False) and getattr(group, "backend", None) == "nccl":
         torch.cuda.synchronize()
         pg = getattr(group, "pg", None)

@@ -14,7 +14,9 @@ the clock stops when it reaches ``--target``.  Prints one JSON line (rank 0).
 ``--cohort hard`` (``data.synthetic.ica_cohort_hard``: connectivity labels, site shifts, label
 noise) is the cohort that separates engines / precisions; ``--compute-path reference`` runs the
 fp32 oracle math (``ops/reference.py``, no fused kernels, eager) on the same device as the
-bf16-fidelity baseline.  The JSON line carries the whole validation-AUC curve.
+bf16-fidelity baseline.  The JSON line carries the whole validation-AUC curve.  ``--engine fedAvg``
+(``--local-steps``, ``--server-momentum``): one-site updates with a round after every K-th of the
+steps between two evaluations and after the last, so every evaluation scores one model.
 """
 from __future__ import annotations
 
@@ -40,7 +42,13 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--effect", "--signal", dest="signal", type=float, default=0.6,
                     help="class-signal amplitude (--effect under torchrun: --signal is ambiguous there)")
-    ap.add_argument("--engine", default="dSGD", choices=["dSGD", "rankDAD", "powerSGD", "topK"])
+    ap.add_argument("--engine", default="dSGD",
+                    choices=["dSGD", "rankDAD", "powerSGD", "topK", "fedAvg"])
+    ap.add_argument("--local-steps", type=int, default=4,
+                    help="fedAvg: fedavg_local_steps; the steps between two evaluations count as "
+                         "an epoch (a round after every K-th of them and after the last)")
+    ap.add_argument("--server-momentum", type=float, default=0.0,
+                    help="fedAvg: fedavg_server_momentum")
     ap.add_argument("--cohort", default="easy", choices=["easy", "hard"])
     ap.add_argument("--label-noise", type=float, default=0.1, help="hard cohort")
     ap.add_argument("--compute-path", default="fused", choices=["fused", "reference"])
@@ -82,8 +90,14 @@ def main():
     flat = FlatParams(model.parameters())
     grp.broadcast(flat.data, 0)
     opt = FusedAdam(flat, lr=a.lr, ema_decay=a.ema_decay)
-    engine = make_engine(a.engine, model, flat, grp, {"precision_bits": "32", "seed": 0})
-    step = TrainStep(model, flat, opt, engine, task="ica",
+    engine = make_engine(a.engine, model, flat, grp,
+                         {"precision_bits": "32", "seed": 0, "fedavg_local_steps": a.local_steps,
+                          "fedavg_server_momentum": a.server_momentum})
+    fed = engine if a.engine == "fedAvg" else None
+    if fed is not None:
+        fed.begin()
+    # (fedAvg: the local updates are one-site steps on the engine's solo dSGD engine)
+    step = TrainStep(model, flat, opt, fed.local if fed is not None else engine, task="ica",
                      use_graph=dev.type == "cuda" and not ref_math)
     g = torch.Generator(device=dev).manual_seed(7 + grp.rank + 100 * a.seed)
 
@@ -114,6 +128,8 @@ def main():
         idx = torch.randint(0, len(Xtr), (a.batch,), device=dev, generator=g)
         step(Xtr[idx], Ytr[idx])
         steps += 1
+        if fed is not None and fed.round_due((steps - 1) % a.eval_every + 1, a.eval_every):
+            fed.round()  # every evaluation sees one model, identical on every site
         if steps % a.eval_every == 0:
             auc = global_auc()
             curve.append([steps, round(auc, 4)])
@@ -143,6 +159,8 @@ def main():
                 ", label_noise=%g" % a.label_noise if a.cohort == "hard" else "")),
             "compute_path": a.compute_path,
             "ema_decay": opt.ema_decay,
+            **({"fedavg_local_steps": fed.local_steps, "fedavg_server_momentum": fed.beta,
+                "fedavg_rounds": fed.rounds} if fed is not None else {}),
             "dtype": "fp32" if ref_math else "bf16",
             "curve": curve,
         }), flush=True)
